@@ -8,7 +8,15 @@ accumulation + 3x3 Procrustes step + convergence test, all on the GPU in ONE
 launch per iteration (the loop state lives on the device; the host only enqueues
 passes).  Inputs and the target index are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--nn grid|brute]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--nn grid|brute] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(`value`, `ms_per_step`, ...).  --dump-outputs DIR writes what the last timed
+call returned (composed transform, transformed source cloud, ...) as
+DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+--full adds every other block of the line: `setup`, per-kernel profile and
+rooflines, `brute_mfma`, `config3`, `config5`, `global_init`, `batch256`,
+`concurrent_pairs`, `cpu_baseline` and `parity` (each takes runs of its own).
 
 --gpus N > 1 without a launcher: this process starts N ranks ITSELF (a child
 `python -m torch.distributed.run --nproc-per-node N ... bench.py`, before any
@@ -159,6 +167,7 @@ def run_icp_steps(pkg, index, src_host, steps, ctx, sd=None):
     out["wall_s"] = time.perf_counter() - t0
     out["n_assoc"] = last["n_assoc"]
     out["T_total"] = last["T_total"]
+    out["last"] = last
     if own_sd:
         sd.free()   # (a cloud handed in is the caller's to release -- after its timed region: releasing device memory is not a step)
     return out
@@ -361,6 +370,24 @@ def setup_leg(pkg, ctx, src, tgt, cell):
             "note": "wall, best of 10; uploads include the host packing + bounding box and the PCIe transfer (1.44 MB per 120k cloud)"}
 
 
+def device_warmup(pkg, ctx, src, tgt, cell):
+    """setup_leg's device work (10 uploads, index builds, lay-outs and compat registrations), untimed and unreported: the plain run's
+    stand-in for it in front of the warm-up steps."""
+    dt = pkg.DeviceCloud.upload(tgt, ctx)
+    for _ in range(10):
+        pkg.DeviceCloud.upload(tgt, ctx).free()
+        pkg.TargetIndex(dt, cell=cell, ctx=ctx).free()
+    index = pkg.TargetIndex(dt, cell=cell, ctx=ctx)
+    for _ in range(10):
+        pkg.DeviceCloud.upload(src, ctx).prepare(index).free()
+        sd = pkg.DeviceCloud.upload(src, ctx)
+        pkg.icp_device(sd, index, np.eye(4))
+        sd.free()
+    ctx.sync()
+    index.free()
+    dt.free()
+
+
 def config3_leg(pkg, ctx, src, tgt):
     """BASELINE configs[2]: 0.2 m voxel filter (Pca_and_Voxel_filter/voxel_filter.py:10-68 as called at :87-90) of both
     120k clouds, device resident, then point-to-point ICP on the filtered clouds (Registration/main.py:211)."""
@@ -549,6 +576,150 @@ def config5_leg(pkg, ctx):
                              "frac": 40.0 * len(world) / (r["device_ms"] / r["iters"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None}}
 
 
+DUMP_ROWS_MAX = 1_000_000   # transformed source rows written by --dump-outputs (24 MB as float64, 32 MB with their ids); larger clouds: a fixed sample
+
+
+def timed_outputs(r, sd):
+    """What a caller of the timed path receives from its last call: the icp_device result and the source cloud it transformed
+    in place (downloaded in row order).  Clouds above DUMP_ROWS_MAX rows: a seeded sample of rows, their ids beside it."""
+    last = r["last"]
+    pts = sd.download()
+    out = {"T_total": last["T_total"], "T": last["T"], "iters": np.array([last["iters"]], dtype=np.float64),
+           "n_assoc": np.array([last["n_assoc"]], dtype=np.float64), "cost": np.array([last["cost"]], dtype=np.float64),
+           "mean_d2": np.array([last["mean_d2"]], dtype=np.float64)}
+    if len(pts) > DUMP_ROWS_MAX:
+        rows = np.sort(np.random.default_rng(0).choice(len(pts), DUMP_ROWS_MAX, replace=False))
+        pts = pts[rows]
+        out["source_transformed_rows"] = rows.astype(np.float64)
+    out["source_transformed"] = pts
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for name, x in arrays.items():
+        x = np.ascontiguousarray(x)
+        assert x.dtype in (np.float32, np.float64), (name, x.dtype)
+        np.save(os.path.join(d, name + ".npy"), x)
+
+
+def full_blocks(a, line, pkg, ctx, index, src, tgt, r, dev_id, world, setup_block, batch256):
+    """--full: every block of the line beyond the headline, into `line` (rank 0).  Each comes from runs of its own after the timed
+    region: a repeat of the timed call under HIP events, a profiled run, the other legs."""
+    n_src = a.points
+    # the pass kernel's average launch period: HIP events on the library's stream around a repeat of the timed call (same
+    # arguments, untimed) / its launches -- ONE launch per iteration, back to back inside the device-resident loop, so this is
+    # the kernel's duration plus the gap to the next launch and the call's init kernel: an upper bound that rocprofv3's
+    # per-kernel average (profiles/r04_grid_kernel_stats.csv) must sit just below.  (The per-launch events of the profiled run
+    # below bracket one launch on an IDLE stream each -- the state is read back after every pass there -- and so include the
+    # ~8 us from the event to the kernel's start: kept as `kernel_us`, not used for the roofline.)
+    sd_ev = pkg.DeviceCloud.upload(src, ctx).prepare(index)
+    ctx.sync()
+    ctx.timer_start()
+    r_ev = run_icp_steps(pkg, index, src, a.steps, ctx, sd=sd_ev)
+    loop_event_us = ctx.timer_stop_ms() * 1e3 / max(r_ev["iters"], 1)
+    sd_ev.free()
+    # per-kernel profile (HIP events on the library's stream) in a separate, untimed run
+    ctx.profile(True)
+    rp = run_icp_steps(pkg, index, src, min(a.steps, 50), ctx)
+    prof_ms, passes = ctx.profile_read()
+    ctx.profile(False)
+    kern = {}
+    if a.nn == "grid":
+        names = ["grid_pass_kernel", "-", "-", "-"]   # ONE launch per iteration: tiles, hard queue, moments, Procrustes, convergence test
+    else:
+        names = ["brute_nn_kernel", "brute_merge_kernel+brute_exact_kernel", "brute_final_kernel", "brute_reduce_partials_kernel"]
+    for nm, ms in zip(names, prof_ms):
+        if nm != "-":
+            kern[nm] = ms / max(passes, 1) * 1e3  # us per launch
+    dom = max(kern, key=kern.get)
+    dom_s = kern[dom] * 1e-6
+    if a.nn == "grid":
+        # the TIMED call's own device time / its launches: the kernels stamp their 100 MHz clock (s_memrealtime) -- first kernel of the
+        # call .. end of its last pass; HIP events recorded by the host around the same call also contain the host's launch latency
+        # in front of the first kernel (`launch_us_hip_events`).  rocprofv3's per-kernel average sits just below both.
+        dom_s = r["device_ms"] / max(r["iters"], 1) * 1e-3
+        algo_bytes = GRID_BYTES_PER_CORR * n_src
+        traffic = None  # HBM bytes per launch from the committed PMC passes (rocprofv3 cannot run inside this process)
+        try:
+            pmc = json.load(open(profile_file("pmc_traffic.json")))
+            traffic = pmc["kernels"][dom].get("hbm_bytes") if a.points == N_POINTS else None
+        except Exception:
+            traffic = None
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": algo_bytes / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": algo_bytes / dom_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
+                    "algorithmic_bytes_per_launch": algo_bytes, "bytes_per_correspondence": GRID_BYTES_PER_CORR,
+                    "launch_us": dom_s * 1e6, "launch_us_hip_events": loop_event_us,
+                    "launch_us_source": f"the timed {a.steps}-iteration call's device time by the kernels' own clock / {a.steps} launches (incl. launch gaps, the call's init "
+                                        "kernel and its unseeded first pass); launch_us_hip_events: HIP events on the library's stream around a repeat of that call "
+                                        "(adds the host's launch latency in front of the first kernel); rocprofv3 --kernel-trace average of the same kernel: "
+                                        "profiles/r04_grid_kernel_stats.csv",
+                    "frac_f64_layout": GRID_LAYOUT_BYTES_PER_CORR * n_src / dom_s / 1e9 / HBM_PEAK_GBS,
+                    "traffic_source": os.path.relpath(profile_file("pmc_traffic.json"), ROOT) + " (separate rocprofv3 --pmc passes of the same command), not measured in this run",
+                    "note": "working set (2 x 3.8 MB) is L2/MALL resident; this kernel is VALU-issue and latency bound, not HBM bound: see roofline_valu"}
+    else:
+        flops = 8.0 * n_src * a.points
+        roofline = {"bound": "mfma", "kernel": dom, "achieved": flops / dom_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": flops / dom_s / 1e12 / FP64_MFMA_PEAK_TFLOPS, "traffic": None}
+    line["pass_kernels_ms_per_iter"] = rp["nn_kernel_ms"] / max(rp["nn_launches"], 1)  # from the profiled (untimed) run
+    line["kernel_us"] = kern
+    line["setup"] = setup_block
+    line["roofline"] = roofline
+    if a.nn == "grid" and "grid_pass_kernel" in kern:
+        # what actually bounds the pass: VALU issue.  Wave instructions per launch from the committed SQ counter passes (rocprofv3
+        # cannot run inside this process), over this run's kernel duration, against one wave64 VALU instruction per SIMD every 2 cycles.
+        try:
+            sqc = json.load(open(profile_file("sq_counters.json")))["kernels"]["grid_pass_kernel"]
+            n_valu = sqc["SQ_INSTS_VALU"] if a.points == N_POINTS else None
+            fpairs, mean_p = filter_pairs_per_pass(pkg, dev_id, src, tgt, a.cell)
+            pass_s = kern["grid_pass_kernel"] * 1e-6
+            line["roofline_valu"] = {"bound": "valu-issue", "kernel": "grid_pass_kernel",
+                                     "achieved": None if n_valu is None else n_valu / pass_s / 1e9, "peak": VALU_ISSUE_PEAK / 1e9,
+                                     "unit": "G wave-instructions/s", "frac": None if n_valu is None else n_valu / pass_s / VALU_ISSUE_PEAK,
+                                     "valu_instructions_per_launch": n_valu,
+                                     "source": os.path.relpath(profile_file("sq_counters.json"), ROOT) + " (SQ_INSTS_VALU, separate rocprofv3 --pmc pass of the same pair)",
+                                     "filter_pairs_per_launch": fpairs, "mean_candidates_per_query": mean_p,
+                                     "note": "whole launch incl. the tail in which most waves wait for the slowest tiles; during the tile stage "
+                                             "(first ~12 us) the SIMDs issue VALU back to back (DESIGN.md 3.1); the filter itself runs on the "
+                                             "matrix cores (v_mfma_f32_32x32x2_f32)"}
+        except Exception as e:  # diagnostics only
+            line["roofline_valu"] = {"error": repr(e)}
+    if batch256 is not None:
+        line["batch256"] = batch256
+    # brute-force MFMA leg (candidate pairs/s + MFMA roofline), N = 1 only
+    if world == 1 and a.nn == "grid" and not a.no_brute:
+        ib = pkg.TargetIndex(pkg.DeviceCloud.upload(tgt, ctx), kind="brute", ctx=ctx)
+        run_icp_steps(pkg, ib, src, 2, ctx)
+        ctx.profile(True)
+        kb = 10
+        t1 = time.perf_counter()
+        rb = run_icp_steps(pkg, ib, src, kb, ctx)
+        eb = time.perf_counter() - t1
+        pm, pp = ctx.profile_read()
+        ctx.profile(False)
+        sweep_s = pm[0] / max(pp, 1) * 1e-3
+        flops = 8.0 * n_src * a.points
+        line["brute_mfma"] = {
+            "ms_per_icp_iter": 1e3 * eb / kb,
+            "correspondences_per_s": n_src * kb / eb,
+            "candidate_pairs_per_s": float(n_src) * a.points / sweep_s,
+            "roofline": {"bound": "mfma", "kernel": "brute_nn_kernel", "achieved": flops / sweep_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS,
+                         "unit": "TFLOP/s", "frac": flops / sweep_s / 1e12 / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
+                         "dtype": "f64 (v_mfma_f64_16x16x4_f64)"},
+        }
+        ib.free()
+    if world == 1 and a.nn == "grid" and not a.no_configs and a.points == N_POINTS:
+        line["config3"] = config3_leg(pkg, ctx, src, tgt)
+        line["config5"] = config5_leg(pkg, ctx)
+        line["global_init"] = global_init_leg(pkg, ctx, src, tgt, dev_id, a.batch_streams, with_batch=not a.no_batch)
+    if world == 1 and a.nn == "grid" and a.in_flight > 1:
+        line["concurrent_pairs"] = concurrent_leg(pkg, dev_id, src, tgt, a.in_flight, min(a.steps, 100))
+    if world == 1 and not a.no_cpu:
+        line["cpu_baseline"] = cpu_baseline(src, tgt)
+        if a.nn == "grid" and a.points <= 200_000:
+            line["parity"] = parity_gates(pkg, index, src, tgt)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -565,6 +736,10 @@ def main():
     ap.add_argument("--no-batch", action="store_true", help="skip the batch256 block (BASELINE configs[3])")
     ap.add_argument("--batch-streams", type=int, default=8, help="contexts (= native worker threads, one sub-batch in flight each) per GPU in the batch256 block")
     ap.add_argument("--no-configs", action="store_true", help="skip the config3 / config5 blocks (BASELINE configs[2] and configs[4])")
+    ap.add_argument("--full", action="store_true", help="also every block beyond the headline (set-up, kernel profile and rooflines, brute_mfma, "
+                                                         "config3 / config5 / global_init, batch256, concurrent_pairs, cpu_baseline, parity); "
+                                                         "the --no-* options above trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed call computed as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
 
     if a.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and "RANK" not in os.environ:
@@ -606,9 +781,15 @@ def main():
         ctx.set_shared(True)
     # the set-up leg (uploads, index builds, one compat registration: what the reference's own usage consists of) is measured FIRST, on every
     # rank: it is a result of its own, and the device's clocks are up when the timed region starts -- the first call of a process on a
-    # device that has idled measured 2 us per iteration more than the following ones (scripts/cold_clock.py), W = 5 warm-up steps are 0.2 ms
-    setup_block = setup_leg(pkg, ctx, src, tgt, a.cell) if a.nn == "grid" else None
-    run_icp_steps(pkg, index, src, a.warmup, ctx)  # untimed warm-up
+    # device that has idled measured 2 us per iteration more than the following ones (scripts/cold_clock.py), W = 5 warm-up steps are 0.2 ms.
+    # Without --full the same device work runs untimed (device_warmup), so that both kinds of run start their timed region alike.
+    setup_block = None
+    if a.nn == "grid" and a.full:
+        setup_block = setup_leg(pkg, ctx, src, tgt, a.cell)
+    elif a.nn == "grid":
+        device_warmup(pkg, ctx, src, tgt, a.cell)
+    if a.warmup > 0:
+        run_icp_steps(pkg, index, src, a.warmup, ctx)  # untimed warm-up
     if dist is not None:  # warm the collective too (communicator and kernel set-up are one-off costs)
         wrec = torch.zeros(18, dtype=torch.float64, device=tdev)
         dist.all_gather([torch.zeros_like(wrec) for _ in range(world)], wrec)
@@ -631,6 +812,8 @@ def main():
         dist.all_gather(allrec, rec)
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        write_outputs(a.dump_outputs, timed_outputs(r, sd_timed))
     sd_timed.free()
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=tdev)
@@ -638,67 +821,13 @@ def main():
         elapsed = float(tmax.item())
 
     batch256 = None
-    if not a.no_batch and a.nn == "grid":
+    if a.full and not a.no_batch and a.nn == "grid":
         batch256 = batch_leg(pkg, torch, dist, rank, world, dev_id, tdev, a.batch_streams)
 
     if rank == 0:
         n_src = a.points
         corr_total = float(n_src) * a.steps * world
         value = corr_total / elapsed
-        # the pass kernel's average launch period: HIP events on the library's stream around a repeat of the timed call (same
-        # arguments, untimed) / its launches -- ONE launch per iteration, back to back inside the device-resident loop, so this is
-        # the kernel's duration plus the gap to the next launch and the call's init kernel: an upper bound that rocprofv3's
-        # per-kernel average (profiles/r04_grid_kernel_stats.csv) must sit just below.  (The per-launch events of the profiled run
-        # below bracket one launch on an IDLE stream each -- the state is read back after every pass there -- and so include the
-        # ~8 us from the event to the kernel's start: kept as `kernel_us`, not used for the roofline.)
-        sd_ev = pkg.DeviceCloud.upload(src, ctx).prepare(index)
-        ctx.sync()
-        ctx.timer_start()
-        r_ev = run_icp_steps(pkg, index, src, a.steps, ctx, sd=sd_ev)
-        loop_event_us = ctx.timer_stop_ms() * 1e3 / max(r_ev["iters"], 1)
-        sd_ev.free()
-        # per-kernel profile (HIP events on the library's stream) in a separate, untimed run
-        ctx.profile(True)
-        rp = run_icp_steps(pkg, index, src, min(a.steps, 50), ctx)
-        prof_ms, passes = ctx.profile_read()
-        ctx.profile(False)
-        kern = {}
-        if a.nn == "grid":
-            names = ["grid_pass_kernel", "-", "-", "-"]   # ONE launch per iteration: tiles, hard queue, moments, Procrustes, convergence test
-        else:
-            names = ["brute_nn_kernel", "brute_merge_kernel+brute_exact_kernel", "brute_final_kernel", "brute_reduce_partials_kernel"]
-        for nm, ms in zip(names, prof_ms):
-            if nm != "-":
-                kern[nm] = ms / max(passes, 1) * 1e3  # us per launch
-        dom = max(kern, key=kern.get)
-        dom_s = kern[dom] * 1e-6
-        if a.nn == "grid":
-            # the TIMED call's own device time / its launches: the kernels stamp their 100 MHz clock (s_memrealtime) -- first kernel of the
-            # call .. end of its last pass; HIP events recorded by the host around the same call also contain the host's launch latency
-            # in front of the first kernel (`launch_us_hip_events`).  rocprofv3's per-kernel average sits just below both.
-            dom_s = r["device_ms"] / max(r["iters"], 1) * 1e-3
-            algo_bytes = GRID_BYTES_PER_CORR * n_src
-            traffic = None  # HBM bytes per launch from the committed PMC passes (rocprofv3 cannot run inside this process)
-            try:
-                pmc = json.load(open(profile_file("pmc_traffic.json")))
-                traffic = pmc["kernels"][dom].get("hbm_bytes") if a.points == N_POINTS else None
-            except Exception:
-                traffic = None
-            roofline = {"bound": "hbm", "kernel": dom, "achieved": algo_bytes / dom_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": algo_bytes / dom_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
-                        "algorithmic_bytes_per_launch": algo_bytes, "bytes_per_correspondence": GRID_BYTES_PER_CORR,
-                        "launch_us": dom_s * 1e6, "launch_us_hip_events": loop_event_us,
-                        "launch_us_source": f"the timed {a.steps}-iteration call's device time by the kernels' own clock / {a.steps} launches (incl. launch gaps, the call's init "
-                                            "kernel and its unseeded first pass); launch_us_hip_events: HIP events on the library's stream around a repeat of that call "
-                                            "(adds the host's launch latency in front of the first kernel); rocprofv3 --kernel-trace average of the same kernel: "
-                                            "profiles/r04_grid_kernel_stats.csv",
-                        "frac_f64_layout": GRID_LAYOUT_BYTES_PER_CORR * n_src / dom_s / 1e9 / HBM_PEAK_GBS,
-                        "traffic_source": os.path.relpath(profile_file("pmc_traffic.json"), ROOT) + " (separate rocprofv3 --pmc passes of the same command), not measured in this run",
-                        "note": "working set (2 x 3.8 MB) is L2/MALL resident; this kernel is VALU-issue and latency bound, not HBM bound: see roofline_valu"}
-        else:
-            flops = 8.0 * n_src * a.points
-            roofline = {"bound": "mfma", "kernel": dom, "achieved": flops / dom_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": flops / dom_s / 1e12 / FP64_MFMA_PEAK_TFLOPS, "traffic": None}
         line = {
             "metric": "correspondence-pairs/sec + ms/ICP-iter, 120k-pt KITTI pair",
             "value": value,
@@ -717,68 +846,13 @@ def main():
                        "points_src": n_src, "points_tgt": a.points, "max_d2": MAX_D2, "cell_m": index.cell},
             "ms_per_icp_iter": 1e3 * elapsed / a.steps,
             "device_ms_per_iter": r["device_ms"] / r["iters"],
-            "pass_kernels_ms_per_iter": rp["nn_kernel_ms"] / max(rp["nn_launches"], 1),  # from the profiled (untimed) run
-            "kernel_us": kern,
             "setup_ms_not_timed": setup_ms,
-            "setup": setup_block,
             "n_assoc_last": int(r["n_assoc"]),
-            "roofline": roofline,
         }
-        if a.nn == "grid" and "grid_pass_kernel" in kern:
-            # what actually bounds the pass: VALU issue.  Wave instructions per launch from the committed SQ counter passes (rocprofv3
-            # cannot run inside this process), over this run's kernel duration, against one wave64 VALU instruction per SIMD every 2 cycles.
-            try:
-                sqc = json.load(open(profile_file("sq_counters.json")))["kernels"]["grid_pass_kernel"]
-                n_valu = sqc["SQ_INSTS_VALU"] if a.points == N_POINTS else None
-                fpairs, mean_p = filter_pairs_per_pass(pkg, dev_id, src, tgt, a.cell)
-                pass_s = kern["grid_pass_kernel"] * 1e-6
-                line["roofline_valu"] = {"bound": "valu-issue", "kernel": "grid_pass_kernel",
-                                         "achieved": None if n_valu is None else n_valu / pass_s / 1e9, "peak": VALU_ISSUE_PEAK / 1e9,
-                                         "unit": "G wave-instructions/s", "frac": None if n_valu is None else n_valu / pass_s / VALU_ISSUE_PEAK,
-                                         "valu_instructions_per_launch": n_valu,
-                                         "source": os.path.relpath(profile_file("sq_counters.json"), ROOT) + " (SQ_INSTS_VALU, separate rocprofv3 --pmc pass of the same pair)",
-                                         "filter_pairs_per_launch": fpairs, "mean_candidates_per_query": mean_p,
-                                         "note": "whole launch incl. the tail in which most waves wait for the slowest tiles; during the tile stage "
-                                                 "(first ~12 us) the SIMDs issue VALU back to back (DESIGN.md 3.1); the filter itself runs on the "
-                                                 "matrix cores (v_mfma_f32_32x32x2_f32)"}
-            except Exception as e:  # diagnostics only
-                line["roofline_valu"] = {"error": repr(e)}
-        if batch256 is not None:
-            line["batch256"] = batch256
         if a.nn == "brute":
             line["candidate_pairs_per_s"] = float(n_src) * a.points * a.steps * world / elapsed
-        # brute-force MFMA leg (candidate pairs/s + MFMA roofline), N = 1 only
-        if world == 1 and a.nn == "grid" and not a.no_brute:
-            ib = pkg.TargetIndex(pkg.DeviceCloud.upload(tgt, ctx), kind="brute", ctx=ctx)
-            run_icp_steps(pkg, ib, src, 2, ctx)
-            ctx.profile(True)
-            kb = 10
-            t1 = time.perf_counter()
-            rb = run_icp_steps(pkg, ib, src, kb, ctx)
-            eb = time.perf_counter() - t1
-            pm, pp = ctx.profile_read()
-            ctx.profile(False)
-            sweep_s = pm[0] / max(pp, 1) * 1e-3
-            flops = 8.0 * n_src * a.points
-            line["brute_mfma"] = {
-                "ms_per_icp_iter": 1e3 * eb / kb,
-                "correspondences_per_s": n_src * kb / eb,
-                "candidate_pairs_per_s": float(n_src) * a.points / sweep_s,
-                "roofline": {"bound": "mfma", "kernel": "brute_nn_kernel", "achieved": flops / sweep_s / 1e12, "peak": FP64_MFMA_PEAK_TFLOPS,
-                             "unit": "TFLOP/s", "frac": flops / sweep_s / 1e12 / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
-                             "dtype": "f64 (v_mfma_f64_16x16x4_f64)"},
-            }
-            ib.free()
-        if world == 1 and a.nn == "grid" and not a.no_configs and a.points == N_POINTS:
-            line["config3"] = config3_leg(pkg, ctx, src, tgt)
-            line["config5"] = config5_leg(pkg, ctx)
-            line["global_init"] = global_init_leg(pkg, ctx, src, tgt, dev_id, a.batch_streams, with_batch=not a.no_batch)
-        if world == 1 and a.nn == "grid" and a.in_flight > 1:
-            line["concurrent_pairs"] = concurrent_leg(pkg, dev_id, src, tgt, a.in_flight, min(a.steps, 100))
-        if world == 1 and not a.no_cpu:
-            line["cpu_baseline"] = cpu_baseline(src, tgt)
-            if a.nn == "grid" and a.points <= 200_000:
-                line["parity"] = parity_gates(pkg, index, src, tgt)
+        if a.full:
+            full_blocks(a, line, pkg, ctx, index, src, tgt, r, dev_id, world, setup_block, batch256)
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

@@ -494,6 +494,19 @@ def gen_readers(syn):
     np.savez_compressed(os.path.join(GOLD, "readers.npz"), **out)
 
 # --------------------------------------------------------------------------
+# The one real cloud the reference ships (Kdtree_Octree/000000.bin, KITTI 4 x f32 records): the statistics
+# tests/test_synthetic_vs_real_scan.py compares the generator with, by that test's own _stats
+# --------------------------------------------------------------------------
+def gen_real_scan():
+    sys.path.insert(0, ROOT)
+    from tests.test_synthetic_vs_real_scan import stats_arrays
+
+    raw = np.fromfile(os.path.join(REF, "Kdtree_Octree", "000000.bin"), dtype=np.float32).reshape(-1, 4)
+    xyz = raw[:, :3].astype(np.float64)
+    print("real scan", xyz.shape)
+    np.savez_compressed(os.path.join(GOLD, "kitti_000000_stats.npz"), **stats_arrays(xyz))
+
+# --------------------------------------------------------------------------
 # G10: ISS keypoints -- Keypoint_detection_ISS/ISS.py:17-75 run unmodified as a script
 # --------------------------------------------------------------------------
 def _install_viewer_stub():
@@ -603,6 +616,8 @@ def main():
         gen_readers(syn)
     if a.only in ("", "iss"):
         gen_iss(syn)
+    if a.only in ("", "scan"):
+        gen_real_scan()
 
 
 if __name__ == "__main__":

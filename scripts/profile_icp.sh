@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_icp
 rm -rf $OUT && mkdir -p $OUT
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/grid_stats -o st -- python3 $R/scripts/prof_pass.py grid 50 > $OUT/grid_stats.log 2>&1
 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/brute_stats -o st -- python3 $R/scripts/prof_pass.py brute 10 > $OUT/brute_stats.log 2>&1
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/bench_stats -o st -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu --no-batch --in-flight 0 > $OUT/bench_stats.log 2>&1
+rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/bench_stats -o st -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu --no-batch --in-flight 0 > $OUT/bench_stats.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $c | tr ' ' '_')
   rocprofv3 --output-format csv --pmc $c -d $OUT/pmc_$tag -o p -- python3 $R/scripts/prof_pass.py grid 10 > $OUT/pmc_$tag.log 2>&1

@@ -1,15 +1,13 @@
-"""Build container only (skipped where /root/reference is absent, i.e. on the GPU box): the synthetic KITTI-shaped generator that
-every bench workload and most fixtures use is tied to the ONE real cloud the reference ships -- Kdtree_Octree/000000.bin, the scan
-BASELINE configs[1] names (read like Kdtree_Octree/lesson2/benchmark.py:16-27, without its transpose) -- through the statistics
-that decide how the search behaves: range distribution, nearest-neighbour spacing, and cell occupancy at the 0.2 m grid cell and
-at the 2.236 m gate radius.  The file is only read, never copied."""
+"""The synthetic KITTI-shaped generator that every bench workload and most fixtures use is tied to the ONE real cloud the reference
+ships -- Kdtree_Octree/000000.bin, the scan BASELINE configs[1] names (read like Kdtree_Octree/lesson2/benchmark.py:16-27, without
+its transpose) -- through the statistics that decide how the search behaves: range distribution, nearest-neighbour spacing, and
+cell occupancy at the 0.2 m grid cell and at the 2.236 m gate radius.  The scan's statistics, by _stats below,
+are the fixture tests/golden/kitti_000000_stats.npz (oracle/ref_harness.py:gen_real_scan reads the scan)."""
 import importlib
-import os
 
 import numpy as np
-import pytest
 
-REAL = "/root/reference/Kdtree_Octree/000000.bin"
+from tests.conftest import load_golden
 
 
 def _stats(p):
@@ -26,12 +24,31 @@ def _stats(p):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(REAL), reason="the reference tree is only present in the build container")
+CELLS = {0.2: "cells_0p2", 5 ** 0.5: "cells_gate"}
+
+
+def stats_arrays(p):
+    """_stats(p) as named float64 arrays (the fixture's layout), with the point count."""
+    s = _stats(p)
+    out = {"n_points": np.array([len(p)], dtype=np.float64)}
+    for k, v in s.items():
+        out[CELLS.get(k, k)] = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    return out
+
+
+def _stats_from_arrays(g):
+    out = {k: g[k] for k in ("range", "nn")}
+    out.update({k: float(g[k][0]) for k in ("r_max", "within20", "within40")})
+    out.update({cell: tuple(g[name]) for cell, name in CELLS.items()})
+    return out
+
+
 def test_generator_statistics_match_the_reference_scan():
     syn = importlib.import_module("point-cloud-process_amd.synthetic")
-    real = np.fromfile(REAL, dtype=np.float32).reshape(-1, 4)[:, :3].astype(np.float64)
-    assert real.shape == (124668, 3)
-    a, b = _stats(real), _stats(syn.kitti_like_scan(len(real), seed=0).astype(np.float64))
+    g = load_golden("kitti_000000_stats.npz")
+    n = int(g["n_points"][0])
+    assert n == 124668                                                 # SURVEY appendix D
+    a, b = _stats_from_arrays(g), _stats(syn.kitti_like_scan(n, seed=0).astype(np.float64))
     # appendix D's own figures for the real scan (the survey's numbers, re-measured)
     assert np.allclose(a["range"], [4.88, 6.74, 10.08, 15.84, 37.81], atol=0.02) and abs(a["nn"][0] - 0.032) < 1e-3
     assert a[0.2][0] == 31890 and a[0.2][3] == 64
