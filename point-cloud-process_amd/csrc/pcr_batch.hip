@@ -604,7 +604,6 @@ int batch_job::launch() {
     const auto t_packed = now();
     hipSetDevice(ctx->device);
     int rc;
-    float* const h_xyz = (float*)hp;
     for (int k = 0; k < m; ++k)
         if (bad_cloud[k] || bad_cloud[m + k]) take[k] = 0;
     // grid parameters per pair: the functions the per-pair path uses, on the same boxes
@@ -713,14 +712,13 @@ int batch_job::launch() {
     // everything crosses PCIe through kernels that read / write the pinned, device-mapped staging block: no copy engine
     hp_dev = nullptr;
     PCR_HIP(ctx, hipHostGetDevicePointer((void**)&hp_dev, hp, 0));
-    static const bool use_dma = getenv("PCR_BATCH_DMA") != nullptr;   // A/B: the packed coordinates by the copy engine instead
     // where the key kernel finds every slot's coordinates: this sub-batch's staging block, or -- a scan an earlier sub-batch of the
     // call owns -- that sub-batch's device copy, behind its key kernel (an event on its stream; its launch is waited for here: the
     // owner is always an EARLIER sub-batch, whose tasks were handed out before this one's, so the wait cannot form a cycle)
     bool owns_shared = false;
     for (int c = 0; c < n_clouds; ++c) {
         if (!room[c]) continue;
-        const float* const own_base = use_dma ? d_in.as<float>() : (const float*)hp_dev;
+        const float* const own_base = (const float*)hp_dev;
         if (alias[c] == -1) { cl[c].src = own_base + 3 * cl[c].off; owns_shared = owns_shared || call->cache[scan_of(c)].shared_later; }
         else if (alias[c] >= 0) cl[c].src = own_base + 3 * cl[alias[c]].off;
         else if (!take[c % m]) cl[c].n_copy = 0;   // (un-taken since the lay-out, and somebody else's scan: nothing to bring over)
@@ -735,9 +733,7 @@ int batch_job::launch() {
     hipLaunchKernelGGL(batch_words_kernel, dim3(8), dim3(256), 0, st, (const unsigned long long*)(hp_dev + off_cl), (unsigned long long*)ds,
                        (unsigned long long)(s_in_end / 8), (unsigned long long)((s_plan + 256) / 8));   // descriptors; counts, offsets and plan zeroed
     const unsigned int blocks_all = (unsigned int)(slots / SLOT), blocks_src = (unsigned int)(src_slots / SLOT), blocks_tgt = blocks_all - blocks_src;
-    if (use_dma) PCR_HIP(ctx, hipMemcpyAsync(d_in.p, h_xyz, xyz_bytes, hipMemcpyHostToDevice, st));
-    static const int keys_blocks_env = getenv("PCR_BATCH_KEYS_BLOCKS") ? atoi(getenv("PCR_BATCH_KEYS_BLOCKS")) : 0;
-    unsigned int keys_grid = keys_blocks_env > 0 ? (unsigned int)keys_blocks_env : 64u;   // (256 pairs, ms per batch: one block per 256 records 6.4-6.8, 1024 blocks 6.1-6.3, 128: 5.9, 64: 5.4, 32: 5.7, 16: 5.9-6.2)
+    unsigned int keys_grid = 64u;   // (256 pairs, ms per batch: one block per 256 records 6.4-6.8, 1024 blocks 6.1-6.3, 128: 5.9, 64: 5.4, 32: 5.7, 16: 5.9-6.2)
     if (keys_grid > blocks_all) keys_grid = blocks_all;
     hipLaunchKernelGGL(batch_keys_kernel, dim3(keys_grid), dim3(SLOT), 0, st, d_in.as<float>(), d_cl, n_clouds,
                        mbits, blocks_all, d_keys.as<unsigned long long>(), d_vals.as<unsigned int>());
@@ -983,16 +979,6 @@ int batch_run(pcr_ctx* const* ctxs, int n_ctx, batch_call& call, const pcr_icp_p
     }
     // (a smaller first sub-batch -- device work after a quarter of a packing time -- measured 5.4 against 4.8-5.1 ms: not adopted)
     std::vector<int64_t> bounds(1, 0);
-    // PCR_BATCH_SPLIT="a,b,c": sizes of the first sub-batches (then `sub` again): experiments with a short first / last one
-    if (const char* split_s = fused ? getenv("PCR_BATCH_SPLIT") : nullptr) {
-        for (const char* p = split_s; *p && bounds.back() < n_pairs;) {
-            char* end = nullptr;
-            const long v = strtol(p, &end, 10);
-            if (end == p) break;
-            if (v > 0) bounds.push_back(bounds.back() + v < n_pairs ? bounds.back() + v : n_pairs);
-            p = *end ? end + 1 : end;
-        }
-    }
     while (bounds.back() < n_pairs) bounds.push_back(bounds.back() + sub < n_pairs ? bounds.back() + sub : n_pairs);
     const int64_t n_sub = (int64_t)bounds.size() - 1;
     std::vector<int32_t> status_own;
@@ -1103,14 +1089,11 @@ int batch_run(pcr_ctx* const* ctxs, int n_ctx, batch_call& call, const pcr_icp_p
         // launches a sub-batch leaves the pool until that sub-batch is done.  Threads are not tied to contexts: more of them pack.
         // Default: two threads per context, at most 16 (a rank's share of the host on an 8-GPU node; 256 pairs on 8 contexts, C call:
         // 8 threads 5.5-5.8 ms, 12: 4.9-5.3, 16: 4.6-4.9, 24: no better), bound to the NUMA node of the device.
-        const char* thr_s = getenv("PCR_BATCH_THREADS");
-        int n_workers = thr_s ? atoi(thr_s) : (2 * n_ctx < 16 ? 2 * n_ctx : (n_ctx > 16 ? n_ctx : 16));
-        if (n_workers < 1) n_workers = 1;
+        int n_workers = 2 * n_ctx < 16 ? 2 * n_ctx : (n_ctx > 16 ? n_ctx : 16);
         if (n_workers > 64) n_workers = 64;
         if ((int64_t)n_workers > n_tasks) n_workers = (int)n_tasks;
         cpu_set_t node_cpus;
-        static const bool no_pin = getenv("PCR_BATCH_NO_PIN") != nullptr;
-        const bool pin = !no_pin && device_numa_cpus(ctxs[0]->device, &node_cpus);
+        const bool pin = device_numa_cpus(ctxs[0]->device, &node_cpus);
         run_pool(n_workers, worker, pin ? &node_cpus : nullptr);
         // what later sub-batches read of earlier ones: back to the arenas now that every stream has been waited for
         for (auto& S : subs)

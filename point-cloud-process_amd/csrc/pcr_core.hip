@@ -53,11 +53,6 @@ int pcr_ctx_create(int device, pcr_ctx** out) {
     hipEventCreate(&c->ev2);
     hipEventCreate(&c->ev3);
     c->h_pinned_bytes = 4096;
-    c->zero_copy = getenv("PCR_NO_ZEROCOPY") == nullptr;
-    if (const char* l = getenv("PCR_ICP_LANES")) c->icp_lanes = atoi(l) < 1 ? 1 : atoi(l);
-    if (c->zero_copy && getenv("PCR_NO_HOSTSUM") == nullptr &&
-        hipHostMalloc((void**)&c->h_slabs, sizeof(double) * PCR_NMOM * PCR_SLABS_PER_LANE * PCR_MAX_LANES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
-        c->h_slabs = nullptr;
     if (hipHostMalloc((void**)&c->h_pinned, c->h_pinned_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
         delete c;
         return PCR_E_NOMEM;
@@ -95,7 +90,6 @@ int pcr_ctx_destroy(pcr_ctx* c) {
     if (c->d_counters) hipFree(c->d_counters);
     if (c->d_cell_counts) hipFree(c->d_cell_counts);
     if (c->h_pinned) hipHostFree(c->h_pinned);
-    if (c->h_slabs) hipHostFree(c->h_slabs);
     if (c->h_state) hipHostFree(c->h_state);
     if (c->h_small) hipHostFree(c->h_small);
     if (c->h_big) hipHostFree(c->h_big);
@@ -108,8 +102,6 @@ int pcr_ctx_destroy(pcr_ctx* c) {
     hipEventDestroy(c->ev3);
     for (int i = 0; i < 5; ++i)
         if (c->pev[i]) hipEventDestroy(c->pev[i]);
-    for (int l = 0; l < PCR_MAX_LANES; ++l)
-        if (c->lane_stream[l]) hipStreamDestroy(c->lane_stream[l]);
     hipStreamDestroy(c->stream);
     delete c;
     return PCR_OK;
@@ -418,15 +410,8 @@ void pcr_dev_free(pcr_ctx* ctx, void* p, size_t bytes) {
             break;
         }
     }
-    // Frees are stream-ordered with later allocations: every user of a block runs on ctx->stream, or on a lane stream
-    // that the ICP pass synchronises before it frees (pcr_grid_icp_pass).
+    // Frees are stream-ordered with later allocations: every user of a block runs on ctx->stream.
     ctx->free_list.push_back({p, bytes});
-}
-
-int pcr_ctx_lanes(pcr_ctx* ctx, int lanes) {
-    for (int l = 0; l < lanes && l < PCR_MAX_LANES; ++l)
-        if (!ctx->lane_stream[l]) PCR_HIP(ctx, hipStreamCreateWithFlags(&ctx->lane_stream[l], hipStreamNonBlocking));
-    return PCR_OK;
 }
 
 int pcr_ensure_scratch(pcr_ctx* ctx, size_t partial_bytes) {

@@ -814,7 +814,6 @@ struct init_job {
     const unsigned int *mra, *mrb;    // row of the smallest norm (lowest row on ties) of either set: the answer for an all-zero query
 };
 constexpr int JOB_SPLITS = 8;
-__device__ static inline long long job_per(long long nb) { return ((nb + JOB_SPLITS - 1) / JOB_SPLITS + FM_TILE - 1) / FM_TILE * FM_TILE; }
 
 // ---- feature matching on the matrix cores, exact.
 // |a - b|^2 = |a|^2 + (|b|^2 - 2 a.b): the bracket is a K = 36 contraction [-2 b_0 .. -2 b_32, |b|^2, 0, 0] . [a_0 .. a_32, 1, 0, 0] -- nine
@@ -1090,15 +1089,6 @@ __global__ void __launch_bounds__(256) feature_match_mfma_jobs_kernel(const init
     }
 }
 
-__global__ void __launch_bounds__(256) feature_match_jobs_kernel(const init_job* __restrict__ jobs, int mutual) {
-    __shared__ double tile[FM_TILE * 33];
-    const init_job J = jobs[blockIdx.z >> 1];
-    const bool back = (blockIdx.z & 1) != 0;
-    if (back && !mutual) return;
-    const long long na = back ? J.nb : J.na, nb = back ? J.na : J.nb;
-    if ((long long)blockIdx.x * 256 >= na) return;   // (the whole block)
-    feature_match_body<33>(back ? J.fb : J.fa, na, back ? J.fa : J.fb, nb, 33, job_per(nb), back ? J.ci_ba : J.ci_ab, back ? J.cd_ba : J.cd_ab, blockIdx.x, blockIdx.y, tile);
-}
 __global__ void __launch_bounds__(256) feature_match_merge_jobs_kernel(const init_job* __restrict__ jobs, int mutual, int splits) {
     const init_job J = jobs[blockIdx.y >> 1];
     const bool back = (blockIdx.y & 1) != 0;
@@ -1144,8 +1134,7 @@ int* fail_word(pcr_ctx* ctx) { return (int*)(ctx->d_counters + 116); }
 // an index: two grid builds per scan -- one per radius, ~20 launches each -- cost several times what the neighbourhoods themselves
 // cost, and a wave reads 4 096 records in 64 trips.  The "view" of such a cloud: its records in row order, levels = 0.
 bool brute_view(const pcr_cloud* cloud, pcr_grid_view* v) {
-    static const bool off = getenv("PCR_HYBRID_GRID") != nullptr;   // A/B: always build the grid
-    if (off || cloud->n > PCR_HYBRID_BRUTE_MAX || cloud->morton_sorted) return false;
+    if (cloud->n > PCR_HYBRID_BRUTE_MAX || cloud->morton_sorted) return false;
     memset(v, 0, sizeof(*v));
     v->pts = cloud->d;
     v->n = cloud->n;
@@ -1431,7 +1420,6 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
         fprintf(stderr, "pcr_global_init_batch: %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
         t_last = now;
     };
-    const bool use_mfma = getenv("PCR_INIT_MATCH_VALU") == nullptr;   // A/B and tests: the matching of the pair stage on the vector ALUs (read per call)
     constexpr int64_t CHUNK_PTS = 16ll << 20;
     constexpr int CHUNK_SCANS = 2048;
     std::vector<scan_slot> slot((size_t)n_clouds);
@@ -1596,31 +1584,25 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
         else
             hipLaunchKernelGGL(fpfh_scans_kernel<NB_CAP>, dim3((unsigned)ng), dim3(64), 0, ctx->stream, V, (long long)ng, g->fpfh_max_nn, (const double*)b_spfh.as<double>(),
                                (const unsigned int*)b_id.as<unsigned int>(), (const double*)b_d2.as<double>(), (const int*)b_cnt.as<int>(), c.fpfh);
-        if (use_mfma) {
-            c.tile_first.assign((size_t)c.n_scans + 1, 0u);
-            for (int k = 0; k < c.n_scans; ++k) c.tile_first[(size_t)k + 1] = c.tile_first[(size_t)k] + (c.first[(size_t)k + 1] - c.first[(size_t)k] + 15u) / 16u;
-            c.tiles = c.tile_first[(size_t)c.n_scans];
-            pcr_dev_block b_tf(ctx), b_dup(ctx);
-            if ((rc = b_dup.alloc(ng ? ng : 1))) break;
-            const size_t op_bytes = 8 * 64 * (size_t)FM_STEPS * (c.tiles ? c.tiles : 1);
-            if ((rc = pcr_dev_alloc(ctx, op_bytes, (void**)&c.op_t)) || (rc = pcr_dev_alloc(ctx, op_bytes, (void**)&c.op_q)) || (rc = pcr_dev_alloc(ctx, 8 * (ng ? ng : 1), (void**)&c.norm2)) ||
-                (rc = pcr_dev_alloc(ctx, 8 * (size_t)(c.n_scans + 1), (void**)&c.max_norm2)) || (rc = pcr_dev_alloc(ctx, 4 * (size_t)(c.n_scans + 1), (void**)&c.min_row)) ||
-                (rc = b_tf.alloc(4 * (size_t)(c.n_scans + 1))))
-                break;
-            if (hipMemcpyAsync(b_tf.p, c.tile_first.data(), 4 * (size_t)(c.n_scans + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-                hipMemsetAsync(c.max_norm2, 0, 8 * (size_t)(c.n_scans + 1), ctx->stream) != hipSuccess) { rc = PCR_E_HIP; break; }
-            hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)c.n_scans), dim3(1024), 0, ctx->stream, (const double*)c.fpfh, (const unsigned int*)c.scan_first, b_dup.as<unsigned char>());
-            if (c.tiles)
-                hipLaunchKernelGGL(mfma_ops_kernel, dim3((unsigned)c.tiles), dim3(64), 0, ctx->stream, (const double*)c.fpfh, (const unsigned int*)c.scan_first, c.n_scans,
-                                   (const unsigned int*)b_tf.as<unsigned int>(), (const unsigned char*)b_dup.as<unsigned char>(), c.op_t, c.op_q, c.norm2, c.max_norm2);
-            hipLaunchKernelGGL(min_norm_row_kernel, dim3((unsigned)c.n_scans), dim3(256), 0, ctx->stream, (const double*)c.norm2, (const unsigned int*)c.scan_first, c.min_row);
-            if (hipGetLastError() != hipSuccess) { rc = PCR_E_HIP; break; }
-            rc = read_fail(ctx);   // (synchronises: the chunk's scratch -- and the tile table -- and the pinned block are free for the next chunk)
-            lap("normals + SPFH + FPFH");
-            continue;
-        }
+        c.tile_first.assign((size_t)c.n_scans + 1, 0u);
+        for (int k = 0; k < c.n_scans; ++k) c.tile_first[(size_t)k + 1] = c.tile_first[(size_t)k] + (c.first[(size_t)k + 1] - c.first[(size_t)k] + 15u) / 16u;
+        c.tiles = c.tile_first[(size_t)c.n_scans];
+        pcr_dev_block b_tf(ctx), b_dup(ctx);
+        if ((rc = b_dup.alloc(ng ? ng : 1))) break;
+        const size_t op_bytes = 8 * 64 * (size_t)FM_STEPS * (c.tiles ? c.tiles : 1);
+        if ((rc = pcr_dev_alloc(ctx, op_bytes, (void**)&c.op_t)) || (rc = pcr_dev_alloc(ctx, op_bytes, (void**)&c.op_q)) || (rc = pcr_dev_alloc(ctx, 8 * (ng ? ng : 1), (void**)&c.norm2)) ||
+            (rc = pcr_dev_alloc(ctx, 8 * (size_t)(c.n_scans + 1), (void**)&c.max_norm2)) || (rc = pcr_dev_alloc(ctx, 4 * (size_t)(c.n_scans + 1), (void**)&c.min_row)) ||
+            (rc = b_tf.alloc(4 * (size_t)(c.n_scans + 1))))
+            break;
+        if (hipMemcpyAsync(b_tf.p, c.tile_first.data(), 4 * (size_t)(c.n_scans + 1), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+            hipMemsetAsync(c.max_norm2, 0, 8 * (size_t)(c.n_scans + 1), ctx->stream) != hipSuccess) { rc = PCR_E_HIP; break; }
+        hipLaunchKernelGGL(dup_rows_kernel, dim3((unsigned)c.n_scans), dim3(1024), 0, ctx->stream, (const double*)c.fpfh, (const unsigned int*)c.scan_first, b_dup.as<unsigned char>());
+        if (c.tiles)
+            hipLaunchKernelGGL(mfma_ops_kernel, dim3((unsigned)c.tiles), dim3(64), 0, ctx->stream, (const double*)c.fpfh, (const unsigned int*)c.scan_first, c.n_scans,
+                               (const unsigned int*)b_tf.as<unsigned int>(), (const unsigned char*)b_dup.as<unsigned char>(), c.op_t, c.op_q, c.norm2, c.max_norm2);
+        hipLaunchKernelGGL(min_norm_row_kernel, dim3((unsigned)c.n_scans), dim3(256), 0, ctx->stream, (const double*)c.norm2, (const unsigned int*)c.scan_first, c.min_row);
         if (hipGetLastError() != hipSuccess) { rc = PCR_E_HIP; break; }
-        rc = read_fail(ctx);   // (synchronises: the chunk's scratch and the pinned block are free for the next chunk)
+        rc = read_fail(ctx);   // (synchronises: the chunk's scratch -- and the tile table -- and the pinned block are free for the next chunk)
         lap("normals + SPFH + FPFH");
     }
     if (rc) { pcr_sync(ctx->stream); release(); return rc; }
@@ -1646,11 +1628,9 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
             if (J.na <= 0 || J.nb <= 0) continue;
             J.src = cs.down + fs; J.tgt = ct.down + ft;
             J.fa = cs.fpfh + 33 * (size_t)fs; J.fb = ct.fpfh + 33 * (size_t)ft;
-            if (use_mfma) {
-                const size_t ts = (size_t)cs.tile_first[(size_t)S.local] * FM_STEPS * 64, tt = (size_t)ct.tile_first[(size_t)T.local] * FM_STEPS * 64;
-                J.ta = cs.op_t + ts; J.qa = cs.op_q + ts; J.n2a = cs.norm2 + fs; J.mxa = (const double*)(cs.max_norm2 + S.local); J.mra = cs.min_row + S.local;
-                J.tb = ct.op_t + tt; J.qb = ct.op_q + tt; J.n2b = ct.norm2 + ft; J.mxb = (const double*)(ct.max_norm2 + T.local); J.mrb = ct.min_row + T.local;
-            }
+            const size_t ts = (size_t)cs.tile_first[(size_t)S.local] * FM_STEPS * 64, tt = (size_t)ct.tile_first[(size_t)T.local] * FM_STEPS * 64;
+            J.ta = cs.op_t + ts; J.qa = cs.op_q + ts; J.n2a = cs.norm2 + fs; J.mxa = (const double*)(cs.max_norm2 + S.local); J.mra = cs.min_row + S.local;
+            J.tb = ct.op_t + tt; J.qb = ct.op_q + tt; J.n2b = ct.norm2 + ft; J.mxb = (const double*)(ct.max_norm2 + T.local); J.mrb = ct.min_row + T.local;
             J.seed = g->ransac.seed;
             // pool offsets (resolved below): ij na | ji nb | ci_ab S*na | ci_ba S*nb | corr 2 na + 4 | inl BATCH   (ints)
             //                                dab na | dba nb | cd_ab S*na | cd_ba S*nb | err2 BATCH | Tout 12 BATCH | state   (doubles)
@@ -1692,9 +1672,8 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
         const unsigned qb = (unsigned)((max_n + 255) / 256);
         // (matrix-core sweep: one split -- 4 waves per 256 queries and direction -- unless a pair or two are all there is)
         const int mfma_splits = (long long)nj * 2 * qb * 4 >= (long long)ctx->cu_count ? 1 : (JOB_SPLITS < 4 ? JOB_SPLITS : 4);
-        if (use_mfma) hipLaunchKernelGGL(feature_match_mfma_jobs_kernel, dim3(qb, mfma_splits, 2 * nj), dim3(256), 0, ctx->stream, d_jobs, mutual, mfma_splits);
-        else hipLaunchKernelGGL(feature_match_jobs_kernel, dim3(qb, JOB_SPLITS, 2 * nj), dim3(256), 0, ctx->stream, d_jobs, mutual);
-        hipLaunchKernelGGL(feature_match_merge_jobs_kernel, dim3(qb, 2 * nj), dim3(256), 0, ctx->stream, d_jobs, mutual, use_mfma ? mfma_splits : JOB_SPLITS);
+        hipLaunchKernelGGL(feature_match_mfma_jobs_kernel, dim3(qb, mfma_splits, 2 * nj), dim3(256), 0, ctx->stream, d_jobs, mutual, mfma_splits);
+        hipLaunchKernelGGL(feature_match_merge_jobs_kernel, dim3(qb, 2 * nj), dim3(256), 0, ctx->stream, d_jobs, mutual, mfma_splits);
         hipLaunchKernelGGL(corr_build_jobs_kernel, dim3(nj), dim3(256), 0, ctx->stream, d_jobs, mutual, 9, g->ransac.max_iteration);
         lap("matching + correspondences");
         ransac_common rcmn;

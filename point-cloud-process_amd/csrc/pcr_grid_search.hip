@@ -15,7 +15,7 @@
 //               device-side work queue for the open queries served by the waves whose tile is done, and the last wave solves
 //               the 3x3 step and tests convergence, so the host is out of the iteration.  grid_drain_kernel: second launch of
 //               the throughput variant.
-//   stand-alone grid_wtile_kernel -> grid_hard_kernel (-> grid_accumulate_kernel): the nn1 API, ungated runs, the host loop.
+//   stand-alone grid_wtile_kernel -> grid_hard_kernel (-> grid_accumulate_kernel): the nn1 API, ungated runs, pcr_icp_moments.
 // Round 1's stage was a 64-query tile per 256-thread block (4 barriers per tile, ~980 staged candidates per query, all
 // resident tiles in lockstep): 40 us for the same pass that takes the wave tiles ~30 us with a third of the hard-stage
 // work; DESIGN.md section 7 keeps its measurements.  Measured alternatives before that, all exact, all slower on the
@@ -1936,22 +1936,16 @@ static void grid_scratch_free(pcr_ctx* ctx, grid_scratch* sc) {
     sc->res_pos = nullptr; sc->res_d2 = nullptr; sc->hard_list = nullptr; sc->prev_xyz = nullptr; sc->items = nullptr; sc->acc = nullptr;
 }
 
+// staged-point cap of a wave tile: the large one when the launch is more than 8 blocks per CU deep
+static unsigned int wtile_point_cap(const pcr_ctx* ctx, int64_t nq) {
+    const int nblocks = (int)((nq + 63) / 64);
+    return (unsigned int)WT_PR * (nblocks > 8 * ctx->cu_count ? WT_ROUNDS_LARGE : WT_ROUNDS_SMALL);
+}
+constexpr unsigned int WT_BUSY_CAP = WT_PR * 48;   // staged-point cap of a tile while the queue of the last pass was long (see grid_pass_kernel)
+constexpr int WT_XCD_REMAP = 1;                     // wtile_block: one contiguous run of the sorted queries per XCD
+
 // Enqueues the search stages on `stream` over the `nq` records at `q` (a whole Morton-sorted cloud or a run of it);
 // leaves res_pos (and res_d2 when the scratch has it) on the device.  `st` != null: device-resident ICP loop.
-static unsigned int wtile_point_cap(const pcr_ctx* ctx, int64_t nq) {
-    static const int wt_rounds_env = getenv("PCR_WT_ROUNDS") ? atoi(getenv("PCR_WT_ROUNDS")) : 0;
-    const int nblocks = (int)((nq + 63) / 64);
-    return (unsigned int)WT_PR * (wt_rounds_env > 0 ? wt_rounds_env : (nblocks > 8 * ctx->cu_count ? WT_ROUNDS_LARGE : WT_ROUNDS_SMALL));
-}
-static unsigned int wtile_busy_cap() {   // PCR_WT_ROUNDS_BUSY: staging rounds of a tile while the queue of the last pass was long (see grid_pass_kernel)
-    static const int env = getenv("PCR_WT_ROUNDS_BUSY") ? atoi(getenv("PCR_WT_ROUNDS_BUSY")) : 0;
-    return (unsigned int)WT_PR * (unsigned int)(env > 0 ? env : 48);
-}
-static int wtile_xcd_remap() {
-    static const int xcd_remap = getenv("PCR_TILE_XCD") ? atoi(getenv("PCR_TILE_XCD")) : 1;
-    return xcd_remap;
-}
-
 static int grid_search_enqueue(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq, hipStream_t stream, const pcr_xform* x, int write_back,
                                double max_d2, bool gated, bool mark, grid_scratch* sc, const pcr_icp_dev_state* st, bool use_prev = false) {
     const int nblocks = (int)((nq + 63) / 64);
@@ -1962,7 +1956,7 @@ static int grid_search_enqueue(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, in
         if (ctx->d_debug) hipMemsetAsync(ctx->d_debug, 0, sizeof(unsigned long long) * ((1 << 16) + 8 * (size_t)nblocks), stream);
         const int wblocks = (int)((nq + 4 * WT_Q - 1) / (4 * WT_Q));
         hipLaunchKernelGGL(grid_wtile_kernel, dim3(wblocks), dim3(256), 0, stream, (const pcr_grid_view*)idx->d_view, q, (long long)nq, x ? *x : xi, (x || st) ? 1 : 0,
-                           write_back, max_d2, gated ? 1 : 0, wtile_xcd_remap(), wtile_point_cap(ctx, nq), sc->res_pos, sc->res_d2, sc->hard_list, sc->hard_count,
+                           write_back, max_d2, gated ? 1 : 0, WT_XCD_REMAP, wtile_point_cap(ctx, nq), sc->res_pos, sc->res_d2, sc->hard_list, sc->hard_count,
                            ctx->d_debug, st, (const wt_xyz*)(use_prev ? sc->prev_xyz : nullptr));
     }
     if (mark) pcr_prof_mark(ctx, 1);
@@ -2005,88 +1999,28 @@ int pcr_grid_nn1(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_xf
 int pcr_grid_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_xform* x, double max_d2, int write_back,
                       double* d_moments) {
     const bool gated = (max_d2 > 0) && std::isfinite(max_d2);
-    const bool was_sorted = qc->morton_sorted;
     int rc = pcr_cloud_morton_sort(ctx, qc, idx->cell);
     if (rc) return rc;
     const int64_t nq = qc->n;
-    // Lanes: the pass over one pair is a chain of three dependent launches and is latency-bound; runs of the sorted
-    // source are independent, so they go down separate streams and overlap each other's stalls.  Every lane reduces its
-    // own moments (fixed order); the host adds the lanes in lane order.  One lane while profiling (per-kernel events).
-    // Host-sum mode (the ICP loop's zero-copy read-back, not while profiling): every block's partial slab goes straight
-    // to pinned host memory and the host adds them after the sync.
-    const bool host_sum = (d_moments == ctx->h_pinned) && !ctx->profile && ctx->h_slabs != nullptr;
-    int lanes = host_sum ? ctx->icp_lanes : 1;
-    if (lanes > PCR_MAX_LANES) lanes = PCR_MAX_LANES;
-    while (lanes > 1 && nq < (int64_t)lanes * 8192) --lanes;
-    if (!host_sum) {
-        grid_scratch sc;
-        rc = grid_search_launch(ctx, idx, qc->d, nq, ctx->stream, ctx->d_counters + PCR_HARD_COUNTERS, x, write_back, max_d2, gated, false, true, &sc);
-        if (rc) return rc;
-        int grid = (int)((nq + 1023) / 1024);  // four queries per thread
-        if (grid > ctx->cu_count) grid = ctx->cu_count;
-        if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * PCR_NMOM * (size_t)grid))) {
-            grid_scratch_free(ctx, &sc);
-            return rc;
-        }
-        // after a write-back pass the cloud already holds the transformed points
-        pcr_prof_mark(ctx, 2);
-        hipLaunchKernelGGL(grid_accumulate_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (const pcr_pt*)qc->d, (long long)nq, *x,
-                           write_back ? 0 : 1, (const unsigned int*)sc.res_pos, max_d2, gated ? 1 : 0, ctx->d_partials, ctx->d_counters + 64,
-                           d_moments, sc.hard_count, (pcr_icp_dev_state*)nullptr, pcr_icp_loop_args{}, (wt_xyz*)nullptr);
-        pcr_prof_mark(ctx, 3);
-        pcr_prof_mark(ctx, 4);
-        PCR_HIP(ctx, hipGetLastError());
-        pcr_prof_finish(ctx);
-        grid_scratch_free(ctx, &sc);
-        return PCR_OK;
-    }
-    if ((rc = pcr_ctx_lanes(ctx, lanes))) return rc;
-    if (!was_sorted) PCR_HIP(ctx, pcr_sync(ctx->stream));  // the sort ran on the main stream
-    grid_scratch sc[PCR_MAX_LANES];
-    int grids[PCR_MAX_LANES];
-    const int64_t per = ((nq + lanes - 1) / lanes + 1023) / 1024 * 1024;
-    int used = 0;
-    for (int l = 0; l < lanes && rc == PCR_OK; ++l) {
-        const int64_t q0 = per * l, q1 = q0 + per < nq ? q0 + per : nq;
-        if (q0 >= q1) break;
-        ++used;
-        hipStream_t st = lanes == 1 ? ctx->stream : ctx->lane_stream[l];
-        rc = grid_search_launch(ctx, idx, qc->d + q0, q1 - q0, st, ctx->d_counters + PCR_HARD_COUNTERS + 1024 * l, x, write_back, max_d2, gated, false, false, &sc[l]);
-        if (rc) break;
-        int grid = (int)((q1 - q0 + 1023) / 1024);
-        if (grid > PCR_SLABS_PER_LANE) grid = PCR_SLABS_PER_LANE;
-        grids[l] = grid;
-        // slabs go straight to pinned host memory; no ticket
-        hipLaunchKernelGGL(grid_accumulate_kernel, dim3(grid), dim3(256), 0, st, idx->view, (const pcr_pt*)(qc->d + q0), (long long)(q1 - q0), *x,
-                           write_back ? 0 : 1, (const unsigned int*)sc[l].res_pos, max_d2, gated ? 1 : 0,
-                           ctx->h_slabs + (size_t)PCR_NMOM * PCR_SLABS_PER_LANE * l, (unsigned int*)nullptr, (double*)nullptr, sc[l].hard_count,
-                           (pcr_icp_dev_state*)nullptr, pcr_icp_loop_args{}, (wt_xyz*)nullptr);
-    }
-    hipError_t e = hipGetLastError();
-    for (int l = 0; l < used; ++l) {
-        const hipError_t es = pcr_sync(lanes == 1 ? ctx->stream : ctx->lane_stream[l]);
-        if (e == hipSuccess) e = es;
-        grid_scratch_free(ctx, &sc[l]);
-    }
+    grid_scratch sc;
+    rc = grid_search_launch(ctx, idx, qc->d, nq, ctx->stream, ctx->d_counters + PCR_HARD_COUNTERS, x, write_back, max_d2, gated, false, true, &sc);
     if (rc) return rc;
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return PCR_E_HIP; }
-    // fixed-order sum on the host: lanes in order, slabs in order, 8 interleaved accumulators then a fixed tree
-    double m[PCR_NMOM];
-    for (int k = 0; k < PCR_NMOM; ++k) m[k] = 0.0;
-    for (int l = 0; l < used; ++l) {
-        const double* slab = ctx->h_slabs + (size_t)PCR_NMOM * PCR_SLABS_PER_LANE * l;
-        double acc[8][PCR_NMOM];
-        for (int j = 0; j < 8; ++j)
-            for (int k = 0; k < PCR_NMOM; ++k) acc[j][k] = 0.0;
-        for (int b2 = 0; b2 < grids[l]; ++b2)
-            for (int k = 0; k < PCR_NMOM; ++k) acc[b2 & 7][k] += slab[(size_t)b2 * PCR_NMOM + k];
-        for (int k = 0; k < PCR_NMOM; ++k)
-            m[k] += ((acc[0][k] + acc[1][k]) + (acc[2][k] + acc[3][k])) + ((acc[4][k] + acc[5][k]) + (acc[6][k] + acc[7][k]));
+    int grid = (int)((nq + 1023) / 1024);  // four queries per thread
+    if (grid > ctx->cu_count) grid = ctx->cu_count;
+    if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * PCR_NMOM * (size_t)grid))) {
+        grid_scratch_free(ctx, &sc);
+        return rc;
     }
-    // hand the sum over the way the single-lane pass does (the caller reads h_pinned, or copies d_moments)
-    if (d_moments == ctx->h_pinned) memcpy(ctx->h_pinned, m, sizeof(m));
-    else PCR_HIP(ctx, hipMemcpyAsync(d_moments, m, sizeof(m), hipMemcpyHostToDevice, ctx->stream));
-    if (d_moments != ctx->h_pinned) PCR_HIP(ctx, pcr_sync(ctx->stream));
+    // after a write-back pass the cloud already holds the transformed points
+    pcr_prof_mark(ctx, 2);
+    hipLaunchKernelGGL(grid_accumulate_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (const pcr_pt*)qc->d, (long long)nq, *x,
+                       write_back ? 0 : 1, (const unsigned int*)sc.res_pos, max_d2, gated ? 1 : 0, ctx->d_partials, ctx->d_counters + 64,
+                       d_moments, sc.hard_count, (pcr_icp_dev_state*)nullptr, pcr_icp_loop_args{}, (wt_xyz*)nullptr);
+    pcr_prof_mark(ctx, 3);
+    pcr_prof_mark(ctx, 4);
+    PCR_HIP(ctx, hipGetLastError());
+    pcr_prof_finish(ctx);
+    grid_scratch_free(ctx, &sc);
     return PCR_OK;
 }
 
@@ -2207,22 +2141,10 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     }
     static_assert(sizeof(pcr_icp_dev_state) <= 8192, "state must fit the pinned staging buffer");
     pcr_icp_dev_state* h_st = (pcr_icp_dev_state*)ctx->h_state;
-    memset(h_st, 0, sizeof(*h_st));
-    pcr_xform_from_T(T0, &h_st->x);
-    for (int i = 0; i < 16; ++i) h_st->T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) h_st->R_last[3 * i + j] = T0[4 * i + j];
-        h_st->t_last[i] = T0[4 * i + 3];
-    }
-    h_st->first = 1;
-    for (int i = 0; i < 9; ++i) h_st->V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    pcr_icp_loop_args la;
-    la.max_iter = params->max_iter; la.min_iter = params->min_iter;
-    la.compat = params->mode == PCR_ICP_COMPAT_MAIN; la.r_metric = params->r_metric;
-    la.r_thres = params->r_thres; la.t_thres = params->t_thres;
+    pcr_icp_state_init(T0, h_st);
+    const pcr_icp_loop_args la = pcr_icp_loop_args_from(params);
     volatile unsigned long long* const h_flag = (volatile unsigned long long*)((char*)ctx->h_state + HOST_FLAG_OFF);
-    static const bool no_notify = getenv("PCR_ICP_NO_NOTIFY") != nullptr;   // A/B: read the state back by kernels behind the chunk instead
-    if (fused && !no_notify) {
+    if (fused) {
         void* dp = nullptr;
         if (hipHostGetDevicePointer(&dp, ctx->h_state, 0) == hipSuccess) pa.host_block = (unsigned long long*)dp;
         *h_flag = 0ull;   // (the stream is idle: the previous call waited for its own flag)
@@ -2255,8 +2177,7 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
         if (chunk > 64) chunk = 64;
         for (int c = 0; c < chunk && rc == PCR_OK; ++c) {
             // from the second pass on, res_pos holds the previous pass's neighbours (same query order, same target)
-            static const bool no_prev = getenv("PCR_NO_PREV") != nullptr;
-            const bool use_prev = enq + c > 0 && !no_prev;
+            const bool use_prev = enq + c > 0;
             // one launch only when it is a single generation of waves (16 per CU at <= 128 VGPRs) with the device to itself: in a
             // launch of several generations most waves may not wait for work (the later tiles need their slots), and the queue
             // would be served by the last generation alone (1 M points: 2.4 ms per pass against 0.32 ms for two launches)
@@ -2269,9 +2190,9 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
                 pa.pass_id = (unsigned int)(enq + c);
                 pa.notify = c == chunk - 1 ? 1u : 0u;
                 // (the busy cap only where the drain launch exists and logs its item counts: two-launch passes)
-                const unsigned int cap_n = wtile_point_cap(ctx, nq), cap_busy = (!inline_queue && cap_n > (unsigned int)(WT_PR * WT_ROUNDS_SMALL)) ? wtile_busy_cap() : cap_n;
+                const unsigned int cap_n = wtile_point_cap(ctx, nq), cap_busy = (!inline_queue && cap_n > (unsigned int)(WT_PR * WT_ROUNDS_SMALL)) ? WT_BUSY_CAP : cap_n;
                 hipLaunchKernelGGL(grid_pass_kernel, dim3(wblocks), dim3(256), 0, ctx->stream, (const pcr_grid_view*)idx->d_view, idx->view, qc->d, (long long)nq,
-                                   params->max_d2, wtile_xcd_remap(), cap_n, cap_busy, sc.res_pos, ctx->d_debug, use_prev ? 1 : 0, inline_queue, pa);
+                                   params->max_d2, WT_XCD_REMAP, cap_n, cap_busy, sc.res_pos, ctx->d_debug, use_prev ? 1 : 0, inline_queue, pa);
                 if (ctx->profile) pcr_prof_mark(ctx, 1);
                 if (!inline_queue) {
                     // 8 blocks of 4 waves per CU, like the stand-alone hard stage
@@ -2351,25 +2272,9 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     if (rc) return rc;
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return PCR_E_HIP; }
     if (h_st->status == PCR_E_HIP) { ctx->last_error = "ICP pass: a wave gave up waiting on the work queue"; return PCR_E_HIP; }
-    double T_cur[16];
-    pcr::T_from_xform(h_st->x, T_cur);
-    if (!la.compat && h_st->status == PCR_OK && !h_st->converged && h_st->it == params->max_iter && params->max_iter > 0) {
-        // icp_template.py:195-198: a non-converged last iteration still updates src_points and homo_mat_total
-        if ((rc = pcr_cloud_transform(ctx, qc, T_cur))) return rc;
-        pcr::T_mul4(T_cur, h_st->T_total, h_st->T_total);
-    }
-    res->iters = h_st->it;
-    res->status = h_st->status;
-    res->n_assoc = h_st->n_assoc;
-    res->cost = h_st->cost;
-    res->mean_d2 = h_st->mean_d2;
-    for (int i = 0; i < h_st->it && i < PCR_ICP_MAX_LOG; ++i) { res->r_diff[i] = h_st->r_diff[i]; res->t_diff[i] = h_st->t_diff[i]; }
-    res->nn_launches = h_st->passes;
+    if ((rc = pcr_icp_finish(ctx, qc, params, h_st, res))) return rc;
     // per-pass kernel time (HIP events around the pass's launches): only measured while pcr_profile_enable is on
     res->nn_kernel_ms = ctx->profile ? (ctx->prof_ms[0] + ctx->prof_ms[1] + ctx->prof_ms[2] + ctx->prof_ms[3]) - prof_before : 0.0;
-    memcpy(res->T_total, h_st->T_total, sizeof(double) * 16);
-    if (la.compat) memcpy(res->T, T_cur, sizeof(T_cur));
-    else memcpy(res->T, h_st->T_total, sizeof(double) * 16);
     return PCR_OK;
 }
 
@@ -2581,11 +2486,9 @@ int pcr_grid_batch_init(pcr_ctx* ctx, const pcr_batch_pass_args* a, const double
 
 int pcr_grid_batch_pass(pcr_ctx* ctx, const pcr_batch_pass_args* a, unsigned int pass_id) {
     if (a->n_tiles == 0) return PCR_OK;
-    static const int rounds_env = getenv("PCR_BATCH_WT_ROUNDS") ? atoi(getenv("PCR_BATCH_WT_ROUNDS")) : 0;
-    const unsigned int pcap = (unsigned int)WT_PR * (rounds_env > 0 ? rounds_env : WT_ROUNDS_LARGE);
-    static const bool no_prev = getenv("PCR_NO_PREV") != nullptr;
+    const unsigned int pcap = (unsigned int)WT_PR * WT_ROUNDS_LARGE;
     pcr_prof_mark(ctx, 0);   // (pcr_profile_enable: HIP events around the three launches; slots 0..2 of pcr_profile_read)
-    hipLaunchKernelGGL(batch_pass_kernel, dim3(a->n_tiles / 4), dim3(256), 0, ctx->stream, *a, wtile_xcd_remap(), pcap, pass_id, (pass_id > 0 && !no_prev) ? 1 : 0);
+    hipLaunchKernelGGL(batch_pass_kernel, dim3(a->n_tiles / 4), dim3(256), 0, ctx->stream, *a, WT_XCD_REMAP, pcap, pass_id, pass_id > 0 ? 1 : 0);
     pcr_prof_mark(ctx, 1);
     const long long want = (long long)a->n_tiles * WT_Q / 4;
     const int g3 = (int)(want < 8ll * ctx->cu_count ? (want < 1 ? 1 : want) : 8ll * ctx->cu_count);

@@ -95,6 +95,48 @@ static int icp_pass(pcr_ctx* ctx, const pcr_index* index, pcr_cloud* qc, const p
     return pcr_brute_icp_pass(ctx, index, qc->d, qc->n, x, max_d2, write_back, d_mom);
 }
 
+void pcr_icp_state_init(const double T0[16], pcr_icp_dev_state* st) {
+    memset(st, 0, sizeof(*st));
+    pcr_xform_from_T(T0, &st->x);   // transform to apply at the top of the next pass; COMPAT returns it (T0, then the last increment)
+    for (int i = 0; i < 16; ++i) st->T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) st->R_last[3 * i + j] = T0[4 * i + j];
+        st->t_last[i] = T0[4 * i + 3];
+    }
+    st->first = 1;
+    for (int i = 0; i < 9; ++i) st->V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+}
+
+pcr_icp_loop_args pcr_icp_loop_args_from(const pcr_icp_params* params) {
+    pcr_icp_loop_args la;
+    la.max_iter = params->max_iter; la.min_iter = params->min_iter;
+    la.compat = params->mode == PCR_ICP_COMPAT_MAIN ? 1 : 0; la.r_metric = params->r_metric;
+    la.r_thres = params->r_thres; la.t_thres = params->t_thres;
+    return la;
+}
+
+int pcr_icp_finish(pcr_ctx* ctx, pcr_cloud* source, const pcr_icp_params* params, pcr_icp_dev_state* st, pcr_icp_result* res) {
+    const bool compat = params->mode == PCR_ICP_COMPAT_MAIN;
+    double T_cur[16];
+    pcr::T_from_xform(st->x, T_cur);
+    if (!compat && st->status == PCR_OK && !st->converged && st->it == params->max_iter && params->max_iter > 0) {
+        // icp_template.py:195-198: a non-converged last iteration still updates src_points and homo_mat_total
+        const int rc = pcr_cloud_transform(ctx, source, T_cur);
+        if (rc) return rc;
+        pcr::T_mul4(T_cur, st->T_total, st->T_total);
+    }
+    res->iters = st->it;
+    res->status = st->status;
+    res->n_assoc = st->n_assoc;
+    res->cost = st->cost;
+    res->mean_d2 = st->mean_d2;
+    for (int i = 0; i < st->it && i < PCR_ICP_MAX_LOG; ++i) { res->r_diff[i] = st->r_diff[i]; res->t_diff[i] = st->t_diff[i]; }
+    res->nn_launches = st->passes;
+    memcpy(res->T_total, st->T_total, sizeof(st->T_total));
+    memcpy(res->T, compat ? T_cur : st->T_total, sizeof(T_cur));
+    return PCR_OK;
+}
+
 extern "C" {
 
 int pcr_icp_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const double* T, double max_d2,
@@ -133,67 +175,33 @@ int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const pcr_i
         if (rs) return rs;
     }
     source->has_bbox = false;
-    const bool compat = params->mode == PCR_ICP_COMPAT_MAIN;
     PCR_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    int rc = PCR_OK;
-    static const bool host_loop_env = getenv("PCR_ICP_HOSTLOOP") != nullptr;
-    if (index->kind == PCR_INDEX_GRID && ctx->icp_lanes == 1 && !host_loop_env) {
+    int rc;
+    if (index->kind == PCR_INDEX_GRID) {
         // grid index: the whole loop runs on the device, the host only enqueues passes (pcr_grid_search.hip)
-        rc = pcr_grid_icp_loop(ctx, index, source, params, T0, res);
+        if ((rc = pcr_grid_icp_loop(ctx, index, source, params, T0, res))) return rc;
     } else {
-        // host loop (brute-force index, per-kernel profiling, search lanes): one synchronisation per iteration
-        double* d_mom = nullptr;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(double) * PCR_NMOM, (void**)&d_mom))) return rc;
+        // brute-force index: one synchronisation per iteration
         pcr_icp_dev_state st;
-        memset(&st, 0, sizeof(st));
-        pcr_xform_from_T(T0, &st.x);   // transform to apply at the top of the next pass; COMPAT returns it (T0, then the last increment)
-        for (int i = 0; i < 16; ++i) st.T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) st.R_last[3 * i + j] = T0[4 * i + j];
-            st.t_last[i] = T0[4 * i + 3];
-        }
-        st.first = 1;
-        for (int i = 0; i < 9; ++i) st.V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        pcr_icp_loop_args la;
-        la.max_iter = params->max_iter; la.min_iter = params->min_iter; la.compat = compat ? 1 : 0; la.r_metric = params->r_metric;
-        la.r_thres = params->r_thres; la.t_thres = params->t_thres;
+        pcr_icp_state_init(T0, &st);
+        const pcr_icp_loop_args la = pcr_icp_loop_args_from(params);
         double nn_ms = 0;
         for (int it = 0; it < params->max_iter && !st.stop; ++it) {
             // main.py:110 / icp_template.py:195: the source is transformed in place, fused into the pass
             if (ctx->profile) PCR_HIP(ctx, hipEventRecord(ctx->ev2, ctx->stream));
             // zero-copy read-back: the pass writes the 160 bytes of moments straight into pinned, device-mapped host memory
-            rc = icp_pass(ctx, index, source, &st.x, params->max_d2, 1, ctx->zero_copy ? ctx->h_pinned : d_mom);
-            if (rc) break;
+            rc = pcr_brute_icp_pass(ctx, index, source->d, source->n, &st.x, params->max_d2, 1, ctx->h_pinned);
+            if (rc) return rc;
             if (ctx->profile) PCR_HIP(ctx, hipEventRecord(ctx->ev3, ctx->stream));
-            if (!ctx->zero_copy) PCR_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, d_mom, sizeof(double) * PCR_NMOM, hipMemcpyDeviceToHost, ctx->stream));
             PCR_HIP(ctx, pcr_sync(ctx->stream));
             float ms = 0;
             if (ctx->profile) hipEventElapsedTime(&ms, ctx->ev2, ctx->ev3);  // per-pass kernel time only while profiling
             nn_ms += ms;
             pcr::icp_step(&st, ctx->h_pinned, index->view.origin, la, st.r_diff, st.t_diff);
         }
-        pcr_dev_free(ctx, d_mom, sizeof(double) * PCR_NMOM);
-        if (rc) return rc;
-        double T_cur[16];
-        pcr::T_from_xform(st.x, T_cur);
-        if (!compat && st.status == PCR_OK && !st.converged && st.it == params->max_iter && params->max_iter > 0) {
-            // icp_template.py:195-198: a non-converged last iteration still updates src_points and homo_mat_total
-            if ((rc = pcr_cloud_transform(ctx, source, T_cur))) return rc;
-            pcr::T_mul4(T_cur, st.T_total, st.T_total);
-        }
-        res->iters = st.it;
-        res->status = st.status;
-        res->n_assoc = st.n_assoc;
-        res->cost = st.cost;
-        res->mean_d2 = st.mean_d2;
-        for (int i = 0; i < st.it; ++i) { res->r_diff[i] = st.r_diff[i]; res->t_diff[i] = st.t_diff[i]; }
+        if ((rc = pcr_icp_finish(ctx, source, params, &st, res))) return rc;
         res->nn_kernel_ms = nn_ms;
-        res->nn_launches = st.passes;
-        memcpy(res->T_total, st.T_total, sizeof(st.T_total));
-        if (compat) memcpy(res->T, T_cur, sizeof(T_cur));
-        else memcpy(res->T, st.T_total, sizeof(st.T_total));
     }
-    if (rc) return rc;
     if (index->kind == PCR_INDEX_GRID && ctx->loop_dev_ms > 0.0) {
         // device-resident loop: its duration by the kernels' own clock (first kernel of the call .. end of the last pass).  No event
         // behind the loop: on this pool a small operation behind the last big kernel starts 16-45 ms late every 10th-30th call

@@ -101,7 +101,7 @@ struct pcr_ctx {
     unsigned long long flag_seq = 0;   // pcr_wait_flag
     long long arena_grow_count = 0;   // hipMalloc calls for arenas since the context was created, and the host time they took
     double arena_grow_us = 0;
-    // pinned host scratch for the per-iteration moment read-back
+    // pinned, device-mapped host scratch: the brute-force ICP pass writes its moments straight into it
     double* h_pinned = nullptr;
     void* h_state = nullptr;              // pinned, device-mapped 8-KiB landing block of the device-resident ICP state (+ its pass log)
     void* h_small = nullptr;              // pinned, device-mapped landing block of pcr_d2h_small
@@ -115,10 +115,6 @@ struct pcr_ctx {
     size_t h_down_half = 0;
     size_t h_pinned_bytes = 0;
     int shared_device = 0;                // pcr_ctx_set_shared: other contexts keep the device busy (two-launch ICP pass)
-    int icp_lanes = 1;                    // runs of the source searched on separate streams per ICP pass (PCR_ICP_LANES)
-    hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
-    double* h_slabs = nullptr;            // pinned, device-mapped: per-block moment slabs of the host-sum ICP pass
-    bool zero_copy = true;  // kernels write small results straight into h_pinned (PCR_NO_ZEROCOPY=1 disables)
     // device scratch for per-block partial moments
     double* d_partials = nullptr;
     size_t d_partials_bytes = 0;
@@ -193,13 +189,10 @@ struct pcr_dev_block {
     ~pcr_dev_block() { free_now(); }
     template <typename T> T* as() const { return (T*)p; }
 };
-constexpr int PCR_MAX_LANES = 4;
-constexpr int PCR_SLABS_PER_LANE = 256;
-// d_counters: words 0..1023 small per-subsystem counters; from word 1024 on, 1024 words per search lane for the
-// hard-list counters (32 counters, one per 128-byte line)
+// d_counters: words 0..1023 small per-subsystem counters; words 1024..2047 the hard-list counters of the grid search
+// (32 counters, one per 128-byte line)
 constexpr int PCR_HARD_COUNTERS = 1024;
-constexpr size_t PCR_COUNTER_BYTES = 4 * (1024 + 1024 * 4);
-PCR_HIDDEN int pcr_ctx_lanes(pcr_ctx* ctx, int lanes);  // creates the lane streams on first use
+constexpr size_t PCR_COUNTER_BYTES = 4 * (1024 + 1024);
 PCR_HIDDEN int pcr_ensure_scratch(pcr_ctx* ctx, size_t partial_bytes);
 PCR_HIDDEN void pcr_xform_from_T(const double* T, pcr_xform* x);
 // profile helpers: mark slot boundary k (0..4) on the stream; finish() syncs and accumulates
@@ -254,7 +247,12 @@ struct pcr_icp_loop_args {
     int max_iter, min_iter, compat, r_metric;
     double r_thres, t_thres;
 };
-// whole ICP loop on the device (grid index); fills res like the host loop of pcr_icp
+// the loop state before the first pass (the device init kernels build the same state from T0)
+PCR_HIDDEN void pcr_icp_state_init(const double T0[16], pcr_icp_dev_state* st);
+PCR_HIDDEN pcr_icp_loop_args pcr_icp_loop_args_from(const pcr_icp_params* params);
+// end of an ICP call from the loop's final state: the non-converged last iteration of the template mode, then every field of res
+// but nn_kernel_ms and device_ms
+PCR_HIDDEN int pcr_icp_finish(pcr_ctx* ctx, pcr_cloud* source, const pcr_icp_params* params, pcr_icp_dev_state* st, pcr_icp_result* res);
 // device -> pageable host memory through a pinned double buffer (large results: a pageable copy runs at ~4.5 GB/s)
 PCR_HIDDEN int pcr_d2h_staged(pcr_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);
 // Open3D's voxel_down_sample of every scan of a chunk at once (pcr_voxel.hip).  d_xyz: the chunk's points, 3 x f32 each, scan behind scan
@@ -273,6 +271,7 @@ constexpr size_t PCR_SMALL_D2H_BYTES = 16384;
 PCR_HIDDEN int pcr_d2h_small(pcr_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);
 PCR_HIDDEN int pcr_wait_flag(pcr_ctx* ctx, double* flag_us);
 PCR_HIDDEN int pcr_d2h_small_enqueue(pcr_ctx* ctx, void* mapped_host_dst, const void* dev_src, size_t bytes);
+// whole ICP loop on the device (grid index); fills res like the host loop of pcr_icp
 PCR_HIDDEN int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_icp_params* params, const double T0[16],
                                  pcr_icp_result* res);
 

@@ -237,8 +237,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     double* const d_lam = b_lam.as<double>();
     const unsigned grid = (unsigned)((n * IG + 255) / 256);
     const bool want_kp = keypoints_out && n_keypoints_out;
-    static const bool host_nms = getenv("PCR_ISS_HOST_NMS") != nullptr;   // A/B: the host loop over a heap of the candidates
-    const bool dev_nms = want_kp && !host_nms && max_keypoints >= 0 && max_keypoints < ISS_NMS_MAX;
+    const bool dev_nms = want_kp && max_keypoints >= 0 && max_keypoints < ISS_NMS_MAX;   // otherwise the host loop over a heap of the candidates
     int* d_cand = nullptr;
     pcr_dev_block b_rec(ctx), b_rec2(ctx), b_tmp(ctx);
     unsigned int* d_cand_count = ctx->d_counters + 124;

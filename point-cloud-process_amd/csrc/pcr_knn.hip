@@ -356,7 +356,7 @@ knn_block_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long
 // level-0 cell and one ring.  A query whose k-th distance lies inside the ball the staged box certainly covers is proven; one
 // that found k points knows a ball that holds its answer, and the next pass stages the box of that ball -- in cells of the
 // finest level that keeps the box small --; one that still lacks k points asks for rings of 4, 16, 64 ... cells.
-// Measured on one box (PCR_KNN_NO_TILES=1 = round 2's path: lane-per-query scan at every level, then the wave-per-query
+// Measured on one box against round 2's path (lane-per-query scan at every level, then the wave-per-query
 // descent), 120 000-point scan: 120 000 other queries, k = 8: 1.76 against 3.05 ms; 20 000 off-surface queries: 1.5 against
 // 9.7 ms (k = 8), 2.8 against 17 (k = 16) -- nothing reaches the descent any more, whose k full descents per query took
 // milliseconds for a handful of far-out queries --; the scan against itself: a tie (1.09 / 1.14 ms at k = 8).
@@ -710,8 +710,7 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
     if (index->kind != PCR_INDEX_GRID) return PCR_E_UNSUPPORTED;
     hipSetDevice(ctx->device);
     int rc;
-    static const bool no_small = getenv("PCR_KNN_NO_SMALL") != nullptr;
-    if (q <= 16 && k <= 16 && !no_small) {
+    if (q <= 16 && k <= 16) {
         // A handful of queries (the reference's API is one per call, kdtree.py:141-172, octree.py:262-306): one query per wave with all
         // 64 lanes on the query's own box (knn_tile_kernel, the second stage of the batched path), queries read from and results
         // written to a pinned, device-mapped block -- one launch, no copies, no device scratch; what it cannot prove (clamped
@@ -748,9 +747,7 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
     int* d_idx = b_idx.as<int>();
     double* d_dist = b_dist.as<double>();
     PCR_HIP(ctx, hipMemcpyAsync(b_q.p, queries, sizeof(double) * 3 * q, hipMemcpyHostToDevice, ctx->stream));
-    static const bool no_block = getenv("PCR_KNN_NO_BLOCK") != nullptr;
-    static const bool no_tiles = getenv("PCR_KNN_NO_TILES") != nullptr;   // A/B: the lane-per-query kernel at every level, then the descent (round 2)
-    if (k <= 16 && q >= 256 && !no_block) {
+    if (k <= 16 && q >= 256) {
         // Batched path, three stages, each handing what it cannot prove to the next through a list:
         //   1. the lane-per-query scan at the finest level(s) only -- a query's own 27 cells: where it is fast and proves the easy majority;
         //   2. ONE QUERY PER WAVE for what it leaves: all 64 lanes scan the query's own box -- its cells and a ring, then the ball its
@@ -761,28 +758,25 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
         unsigned int* d_cnt_d = ctx->d_counters + 127;   // queries stage 1 left
         pcr_dev_block b_redo2(ctx), b_redo4(ctx), b_kth(ctx);
         if ((rc = b_redo.alloc(sizeof(int) * q)) || (rc = b_redo2.alloc(sizeof(int) * q)) || (rc = b_redo4.alloc(sizeof(int) * q)) || (rc = b_kth.alloc(sizeof(double) * q))) return rc;
-        static const bool no_seed = getenv("PCR_KNN_NO_SEED") != nullptr;   // A/B: the second stage starts over at the query's own 27 cells
-        double* d_kth = no_seed ? nullptr : b_kth.as<double>();
+        double* d_kth = b_kth.as<double>();   // stage 1 hands the k-th distance it found to stage 2 as the first ball
         int *d_redo_a = b_redo.as<int>(), *d_redo_b = b_redo2.as<int>(), *d_redo_d = b_redo4.as<int>();
         PCR_HIP(ctx, hipMemsetAsync(d_cnt_a, 0, 3 * sizeof(unsigned int), ctx->stream));
         const unsigned gb = (unsigned)((q + 255) / 256);
-        if (!no_tiles) {
-            const int lv_first = k > 8 ? 1 : 0;   // (k = 16, a scan against itself: 44 000 of 120 000 queries are left at level 0)
-            unsigned gw = (unsigned)((q + 3) / 4);
-            if (gw > 8u * (unsigned)ctx->cu_count) gw = 8u * (unsigned)ctx->cu_count;   // (a fixed grid strides over the list: its length is only known on the device)
-            if (k <= 8) {
-                hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
-                                   (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
-                hipLaunchKernelGGL((knn_tile_kernel<8, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
-                                   (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
-            } else {
-                hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
-                                   (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
-                hipLaunchKernelGGL((knn_tile_kernel<16, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
-                                   (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
-            }
+        const int lv_first = k > 8 ? 1 : 0;   // (k = 16, a scan against itself: 44 000 of 120 000 queries are left at level 0)
+        unsigned gw = (unsigned)((q + 3) / 4);
+        if (gw > 8u * (unsigned)ctx->cu_count) gw = 8u * (unsigned)ctx->cu_count;   // (a fixed grid strides over the list: its length is only known on the device)
+        if (k <= 8) {
+            hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
+                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
+            hipLaunchKernelGGL((knn_tile_kernel<8, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
+                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
+        } else {
+            hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
+                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
+            hipLaunchKernelGGL((knn_tile_kernel<16, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
+                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
         }
-        const int* todo = no_tiles ? nullptr : d_redo_a;
+        const int* todo = d_redo_a;
         if (k <= 8)
             hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
                                (const unsigned int*)d_cnt_a, PCR_KNN_LV, (double*)nullptr);

@@ -225,8 +225,7 @@ int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out
     if (e[0] < e[1]) std::swap(e[0], e[1]);
     if (e[1] < e[2]) std::swap(e[1], e[2]);
     if (e[0] < e[1]) std::swap(e[0], e[1]);
-    double factor = 1.8;
-    if (const char* f = getenv("PCR_NORMALS_CELL_FACTOR")) factor = atof(f);
+    const double factor = 1.8;
     const double cell = (e[0] * e[1] > 0) ? factor * sqrt((double)k / 5.0 * e[0] * e[1] / (double)n) : 0.0;
     pcr_index* idx = nullptr;
     rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, cell, &idx);
