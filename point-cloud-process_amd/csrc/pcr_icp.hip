@@ -95,18 +95,6 @@ static int icp_pass(pcr_ctx* ctx, const pcr_index* index, pcr_cloud* qc, const p
     return pcr_brute_icp_pass(ctx, index, qc->d, qc->n, x, max_d2, write_back, d_mom);
 }
 
-void pcr_icp_state_init(const double T0[16], pcr_icp_dev_state* st) {
-    memset(st, 0, sizeof(*st));
-    pcr_xform_from_T(T0, &st->x);   // transform to apply at the top of the next pass; COMPAT returns it (T0, then the last increment)
-    for (int i = 0; i < 16; ++i) st->T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) st->R_last[3 * i + j] = T0[4 * i + j];
-        st->t_last[i] = T0[4 * i + 3];
-    }
-    st->first = 1;
-    for (int i = 0; i < 9; ++i) st->V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-}
-
 pcr_icp_loop_args pcr_icp_loop_args_from(const pcr_icp_params* params) {
     pcr_icp_loop_args la;
     la.max_iter = params->max_iter; la.min_iter = params->min_iter;
@@ -183,7 +171,8 @@ int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const pcr_i
     } else {
         // brute-force index: one synchronisation per iteration
         pcr_icp_dev_state st;
-        pcr_icp_state_init(T0, &st);
+        memset(&st, 0, sizeof(st));
+        pcr::icp_state_from_T0(T0, &st);
         const pcr_icp_loop_args la = pcr_icp_loop_args_from(params);
         double nn_ms = 0;
         for (int it = 0; it < params->max_iter && !st.stop; ++it) {

@@ -1,5 +1,6 @@
-// One step of the ICP driver, shared by the host loop (pcr_icp.hip: brute-force index, profiling) and the device
-// loop (last block of grid_accumulate_kernel): compose the transform just applied, Procrustes from the moments,
+// The ICP driver's loop state, shared by the host loop (pcr_icp.hip: brute-force index) and the device loops (the
+// finishing wave of the one-launch pass (pass_finish), batch_finish_kernel, the last block of grid_accumulate_kernel):
+// the state before the first pass, and one step -- compose the transform just applied, Procrustes from the moments,
 // convergence test and bookkeeping -- Registration/main.py:125-154 (COMPAT) / icp_template.py:166-198 (TOTAL).
 #pragma once
 #include <cstddef>
@@ -28,6 +29,22 @@ __host__ __device__ inline void T_mul4(const double A[16], const double B[16], d
             r[4 * i + j] = s;
         }
     for (int i = 0; i < 16; ++i) C[i] = r[i];
+}
+
+// The loop state before the first pass, on a state that is already zero (each caller zeroes it its own way): the first pass applies
+// T0, which COMPAT returns until the first step replaces it; T_total starts at the identity, V (warm start of the first solve) too.
+__host__ __device__ inline void icp_state_from_T0(const double T0[16], pcr_icp_dev_state* st) {
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) {
+            st->x.r[3 * i + j] = T0[4 * i + j];
+            st->R_last[3 * i + j] = T0[4 * i + j];
+        }
+        st->x.t[i] = T0[4 * i + 3];
+        st->t_last[i] = T0[4 * i + 3];
+    }
+    for (int i = 0; i < 16; ++i) st->T_total[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int i = 0; i < 9; ++i) st->V[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    st->first = 1;
 }
 
 // `m` = the 20 accumulated moments of the pass that just applied st->x to the source.  Only the head of *st (everything

@@ -247,8 +247,6 @@ struct pcr_icp_loop_args {
     int max_iter, min_iter, compat, r_metric;
     double r_thres, t_thres;
 };
-// the loop state before the first pass (the device init kernels build the same state from T0)
-PCR_HIDDEN void pcr_icp_state_init(const double T0[16], pcr_icp_dev_state* st);
 PCR_HIDDEN pcr_icp_loop_args pcr_icp_loop_args_from(const pcr_icp_params* params);
 // end of an ICP call from the loop's final state: the non-converged last iteration of the template mode, then every field of res
 // but nn_kernel_ms and device_ms
