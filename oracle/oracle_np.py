@@ -253,6 +253,93 @@ def radius_bruteforce(db, query, r):
     return order, d[order]
 
 
+# ------------------------------------------ k-NN / radius in the kernels' exact order
+KD_WORKERS = 16   # (cKDTree thread pools: a GPU-box command may use 16 CPUs; -1 would size the pool by the whole host)
+
+
+def _knn_rows(D, cols_of, k):
+    """First k of every row of D (squared distances; cols_of(row, col) -> point index) in (d2, index) order.  Candidates are
+    every entry <= the row's k-th value, so ties through the k-th slot are all seen."""
+    nr, nc = D.shape
+    kk = min(k, nc)
+    kth = np.partition(D, kk - 1, axis=1)[:, kk - 1]
+    rows, cols = np.nonzero(D <= kth[:, None])
+    pid = cols_of(rows, cols)
+    d2 = D[rows, cols]
+    order = np.lexsort((pid, d2, rows))
+    rows, pid, d2 = rows[order], pid[order], d2[order]
+    start = np.searchsorted(rows, np.arange(nr))
+    rank = np.arange(len(rows)) - start[rows]
+    keep = rank < kk
+    idx = np.zeros((nr, k), dtype=np.int64)
+    out = np.full((nr, k), -1.0)
+    idx[rows[keep], rank[keep]] = pid[keep]
+    out[rows[keep], rank[keep]] = d2[keep]
+    return idx, out
+
+
+def knn_exact(db, queries, k, brute_max_n=30000, chunk_elems=1 << 22):
+    """The k-NN kernels' contract (pcr_knn.hip:5-8, better() in pcr_grid_dev.h): per query the k points smallest in
+    (d2, index), d2 = dist2_direct, reported as sqrt(d2) -> (idx int64 (Q,k), dist (Q,k)).  Unfilled slots hold (1e10, 0)
+    like KNNResultSet (result_set.py:19-22).  Ordered by d2, not by sqrt(d2): distinct d2 can share one sqrt.
+    Clouds of up to `brute_max_n` points: chunked brute force.  Larger ones: k + 8 candidates from cKDTree recomputed
+    exactly; a row whose last candidate does not clearly exceed its k-th d2 (a tie could reach past the candidates) is
+    redone by brute force."""
+    db = np.asarray(db, dtype=np.float64)[:, :3]
+    q = np.atleast_2d(np.asarray(queries, dtype=np.float64))[:, :3]
+    n, nq = len(db), len(q)
+    idx = np.zeros((nq, k), dtype=np.int64)
+    d2 = np.full((nq, k), -1.0)
+
+    def brute(rows):
+        step = max(1, chunk_elems // max(n, 1))
+        for s in range(0, len(rows), step):
+            r = rows[s : s + step]
+            D = dist2_direct(q[r][:, None, :], db[None, :, :])
+            idx[r], d2[r] = _knn_rows(D, lambda _rw, c: c, k)
+
+    if n <= brute_max_n or n <= k + 8:
+        brute(np.arange(nq))
+    else:
+        m = k + 8
+        _, cand = cKDTree(db).query(q, k=m, workers=KD_WORKERS)
+        cand = cand.reshape(nq, m)
+        D = dist2_direct(q[:, None, :], db[cand])
+        idx, d2 = _knn_rows(D, lambda rw, c: cand[rw, c], k)
+        kth = d2[:, k - 1]
+        redo = np.flatnonzero(~(D.max(axis=1) > kth * (1.0 + 1e-12)))
+        if len(redo):
+            brute(redo)
+    filled = d2 >= 0
+    dist = np.where(filled, np.sqrt(np.where(filled, d2, 0.0)), 1e10)
+    idx[~filled] = 0
+    return idx, dist
+
+
+def radius_exact(db, queries, r):
+    """The radius kernels' contract (pcr_knn.hip radius_scan, pcr_radius / pcr_radius_small): per query every point with
+    !(sqrt(d2) > r), in ascending (sqrt(d2), index) -> (offsets int64 (Q+1,), idx int64 (M,), dist (M,)).  Candidates come
+    from cKDTree at a slightly larger radius and are filtered exactly."""
+    db = np.asarray(db, dtype=np.float64)[:, :3]
+    q = np.atleast_2d(np.asarray(queries, dtype=np.float64))[:, :3]
+    rc = float(r) * (1.0 + 1e-9) + 1e-12
+    lists = cKDTree(db).query_ball_point(q, rc, workers=KD_WORKERS)
+    offs = np.zeros(len(q) + 1, dtype=np.int64)
+    out_i, out_d = [], []
+    for j, c in enumerate(lists):
+        c = np.asarray(c, dtype=np.int64)
+        d = np.sqrt(dist2_direct(q[j][None, :], db[c]))
+        keep = ~(d > r)
+        c, d = c[keep], d[keep]
+        o = np.lexsort((c, d))
+        out_i.append(c[o])
+        out_d.append(d[o])
+        offs[j + 1] = offs[j] + len(c)
+    idx = np.concatenate(out_i) if out_i else np.zeros(0, dtype=np.int64)
+    dist = np.concatenate(out_d) if out_d else np.zeros(0)
+    return offs, idx, dist
+
+
 # ----------------------------------------------------------------------- ISS
 def iss_oracle(points, radius=0.5, lambda21=0.5, lambda32=0.5, non_max_radius=0.5, iss_count=20):
     """Keypoint_detection_ISS/ISS.py:35-73 restated ("parity unpinned": see module docstring).

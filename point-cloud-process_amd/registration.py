@@ -66,20 +66,36 @@ class KDTreeFlann:
     """o3d.geometry.KDTreeFlann(target) (main.py:105): device-resident exact NN index."""
 
     def __init__(self, target, kind="grid", cell=0.0, ctx=None):
-        self.index = target if isinstance(target, TargetIndex) else TargetIndex(points_of(target), kind=kind, cell=cell, ctx=ctx)
+        # Squared distances are the exact (dx*dx + dy*dy) + dz*dz of the neighbours found, recomputed from a host copy of the
+        # target (Open3D's KDTreeFlann keeps its own copy too): squaring the reported sqrt(d2) misses d2 by an ulp about half
+        # the time.  Wrapped around an existing TargetIndex there are no host coordinates: k = 1 only (nn1 returns d2 itself).
+        if isinstance(target, TargetIndex):
+            self.index, self._pts = target, None
+        else:
+            self._pts = np.array(points_of(target)[:, :3], dtype=np.float64)
+            self.index = TargetIndex(self._pts, kind=kind, cell=cell, ctx=ctx)
+
+    def _d2(self, q, idx):
+        if self._pts is None:
+            raise ValueError("KDTreeFlann over a TargetIndex has no target coordinates for squared distances: build it from the points")
+        d = q - self._pts[idx]
+        return (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
 
     def search_knn_vector_3d(self, query, k):
         """-> [k, idx list, SQUARED distance list] like Open3D (main.py:117-119)."""
         q = np.asarray(query, dtype=np.float64).reshape(1, 3)
-        idx, dist = self.index.knn(q, int(k))
+        if int(k) == 1 and self._pts is None:
+            idx, d2 = self.index.nn1(q)
+            return [1, idx.tolist(), d2.tolist()]
+        idx, _ = self.index.knn(q, int(k))
         kk = min(int(k), self.index.n)
-        return [kk, idx[0, :kk].tolist(), (dist[0, :kk] ** 2).tolist()]
+        return [kk, idx[0, :kk].tolist(), self._d2(q, idx[0, :kk]).tolist()]
 
     def search_radius_vector_3d(self, query, radius):
         """-> [k, idx list, SQUARED distance list], ascending distance (Final_Project/scripts/extract.py:519-524)."""
         q = np.asarray(query, dtype=np.float64).reshape(1, 3)
-        _, idx, dist = self.index.radius(q, float(radius))
-        return [len(idx), idx.tolist(), (dist ** 2).tolist()]
+        _, idx, _ = self.index.radius(q, float(radius))
+        return [len(idx), idx.tolist(), self._d2(q, idx).tolist()]
 
     def search_hybrid_vector_3d(self, query, radius, max_nn):
         """-> the max_nn nearest of the radius result (Open3D KDTreeSearchParamHybrid)."""

@@ -193,11 +193,13 @@ def test_knn_radius_fuzz(pcp, oracle, case):
     idx, dist = pcp.knn_search_batch(root, q, k)
     r = float(np.median(dist[:, min(k, n) - 1])) if n >= 1 else 1.0
     offs, ridx, rdist = pcp.radius_search_batch(root, q, r)
+    ei, ed = oracle.knn_exact(db, q, k)        # (d2, index) order: tie slots included
+    assert np.array_equal(dist, ed) and np.array_equal(idx, ei)
+    eo, eri, erd = oracle.radius_exact(db, q, r)
+    assert np.array_equal(offs, eo) and np.array_equal(ridx, eri) and np.array_equal(rdist, erd)   # in order, not as sets
     for j in range(len(q)):
         oi, od = oracle.knn_bruteforce(db, q[j], k)
         assert np.array_equal(dist[j], od)
-        ok = np.r_[True, od[1:] != od[:-1]] & np.r_[od[:-1] != od[1:], True] & (od < 1e10)   # positions not involved in a distance tie
-        assert np.array_equal(idx[j][ok], oi[ok])
         ri, rd = oracle.radius_bruteforce(db, q[j], r)
         s, e = offs[j], offs[j + 1]
-        assert e - s == len(ri) and np.array_equal(rdist[s:e], rd) and set(ridx[s:e].tolist()) == set(np.asarray(ri).tolist())
+        assert e - s == len(ri) and np.array_equal(rdist[s:e], rd) and np.array_equal(ridx[s:e], ri)

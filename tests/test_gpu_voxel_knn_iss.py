@@ -99,9 +99,8 @@ def test_knn_batch_properties(pcp, oracle, syn):
     q = db[rng.integers(0, len(db), 300)] + rng.normal(0, 0.05, (300, 3))
     idx, dist = pcp.knn_search_batch(root, q, 8)
     assert (np.diff(dist, axis=1) >= 0).all()  # ascending
-    for i in range(0, 300, 25):
-        oi, od = oracle.knn_bruteforce(db, q[i], 8)
-        assert np.array_equal(idx[i], oi) and np.allclose(dist[i], od, rtol=1e-14, atol=0)
+    ei, ed = oracle.knn_exact(db, q, 8)        # every query, every slot, bit for bit
+    assert np.array_equal(idx, ei) and np.array_equal(dist, ed)
     off, ridx, rdist = pcp.radius_search_batch(root, q[:50], 0.7)
     for i in range(50):
         oi, od = oracle.radius_bruteforce(db, q[i], 0.7)
@@ -111,9 +110,19 @@ def test_knn_batch_properties(pcp, oracle, syn):
     idx, dist = pcp.knn_search_batch(small, q[:3], 8)
     assert (dist[:, 5:] == 1e10).all() and (idx[:, 5:] == 0).all()
     # Open3D-style wrapper used by main.py:117 returns SQUARED distances
+    # (the exact d2, not the square of the reported sqrt(d2): that differs by an ulp about half the time)
     tree = pcp.KDTreeFlann(db)
     k, ii, dd = tree.search_knn_vector_3d(q[0], 1)
-    assert k == 1 and abs(dd[0] - oracle.dist2_direct(q[0], db[ii[0]])) < 1e-15
+    assert k == 1 and ii == [int(ei[0, 0])] and dd == [oracle.dist2_direct(q[0], db[ii[0]])]
+    for kk in (2, 8, 16, 40):
+        for j in range(12):
+            k, ii, dd = tree.search_knn_vector_3d(q[j], kk)
+            ej, _ = oracle.knn_exact(db, q[j:j + 1], kk)
+            assert k == kk and ii == ej[0].tolist()
+            assert np.array_equal(np.array(dd), oracle.dist2_direct(q[j], db[ii])), (kk, j)
+    over = pcp.KDTreeFlann(pcp.TargetIndex(db))       # around an existing index: k = 1 through nn1, exact as well
+    k, ii, dd = over.search_knn_vector_3d(q[1], 1)
+    assert k == 1 and ii == [int(ei[1, 0])] and dd == [oracle.dist2_direct(q[1], db[ii[0]])]
 
 
 def test_iss_matches_the_reference_script_golden(pcp, golden):
@@ -341,6 +350,9 @@ def test_kdtreeflann_radius_search(pcp, oracle, syn):
     k, idx, d2 = tree.search_radius_vector_3d(pts[123] + 0.01, 1.5)
     ref = np.flatnonzero(np.linalg.norm(pts - (pts[123] + 0.01), axis=1) <= 1.5)
     assert k == len(ref) and set(idx) == set(ref.tolist()) and np.all(np.diff(d2) >= 0)
+    offs, ei, _ = oracle.radius_exact(pts, (pts[123] + 0.01)[None, :], 1.5)
+    assert idx == ei.tolist()                                                    # ascending (sqrt(d2), index)
+    assert np.array_equal(np.array(d2), oracle.dist2_direct(pts[123] + 0.01, pts[idx]))   # the exact d2
     k2, idx2, _ = tree.search_hybrid_vector_3d(pts[123] + 0.01, 1.5, 10)
     assert k2 == min(10, k) and idx2 == idx[:k2]
 

@@ -220,3 +220,99 @@ def test_iss_oracle_matches_the_reference_script(oracle):
         assert np.allclose(lam[srt, 2], g[f"{tag}_sorted_lambda3"], rtol=1e-9, atol=0), tag
         assert len(kp) <= int(cap) + 1
     assert len(g["sparse_iss_idx"]) < 21 and len(g["object_iss_idx"]) == 21     # both sides of the ISS.py:72-73 break
+
+
+# ------------------------------------------- exact k-NN / radius oracles (kernel order)
+def _lattice(rng, n, step=0.25, side=12):
+    return rng.integers(0, side, (n, 3)).astype(np.float64) * step
+
+
+def test_knn_exact_matches_bruteforce_and_orders_by_d2(oracle):
+    rng = np.random.default_rng(11)
+    db = rng.uniform(-5, 5, (3000, 3))
+    q = np.concatenate([rng.uniform(-6, 6, (40, 3)), db[:5]])
+    for k in (1, 8, 17, 3000, 3005):
+        idx, dist = oracle.knn_exact(db, q, k)
+        assert idx.shape == dist.shape == (len(q), k)
+        for j in range(len(q)):
+            oi, od = oracle.knn_bruteforce(db, q[j], k)     # no ties on this cloud: the same order
+            assert np.array_equal(idx[j], oi) and np.array_equal(dist[j], od), (k, j)
+    # a lattice full of ties: ascending (d2, index) in every slot, the k-th tie group cut by index
+    db = _lattice(rng, 4000)
+    q = np.concatenate([db[:20], db[20:40] + 0.125])
+    idx, dist = oracle.knn_exact(db, q, 20)
+    for j in range(len(q)):
+        d2 = oracle.dist2_direct(q[j], db)
+        order = np.lexsort((np.arange(len(db)), d2))[:20]
+        assert np.array_equal(idx[j], order) and np.array_equal(dist[j], np.sqrt(d2[order]))
+    # distinct d2 that share one sqrt (2.5 and nextafter(2.5, 3) do): the order is the d2 order, not the sqrt order
+    assert np.sqrt(2.5) == np.sqrt(np.nextafter(2.5, 3.0))
+    u = rng.normal(size=(4000, 3))
+    db = u / np.linalg.norm(u, axis=1, keepdims=True) * np.sqrt(2.5)
+    d2 = oracle.dist2_direct(np.zeros(3), db)
+    idx, dist = oracle.knn_exact(db, np.zeros((1, 3)), len(db))
+    assert np.all(np.diff(d2[idx[0]]) >= 0)
+    by_sqrt = np.lexsort((np.arange(len(db)), np.sqrt(d2)))
+    assert not np.array_equal(idx[0], by_sqrt)                # (the two orders really differ here)
+    assert np.array_equal(dist[0], np.sqrt(d2[by_sqrt]))      # ... while the reported distances agree
+
+
+def test_knn_exact_fewer_points_than_k(oracle):
+    db = np.array([[0.0, 0, 0], [1.0, 0, 0], [1.0, 0, 0]])
+    idx, dist = oracle.knn_exact(db, np.array([[0.9, 0, 0], [5.0, 5, 5]]), 5)
+    assert idx[0].tolist() == [1, 2, 0, 0, 0] and dist[0, 3:].tolist() == [1e10, 1e10]
+    assert (dist[:, :3] < 1e10).all() and (dist[:, 3:] == 1e10).all() and (idx[:, 3:] == 0).all()
+
+
+def test_knn_exact_kdtree_path_matches_bruteforce_on_ties(oracle):
+    """The cKDTree path (large clouds) against the brute force, forced on a small lattice cloud full of ties: candidates
+    recomputed exactly, rows whose ties reach past the candidates redone."""
+    rng = np.random.default_rng(12)
+    db = np.concatenate([_lattice(rng, 6000), _lattice(rng, 200)])             # exact duplicates too
+    q = np.concatenate([db[:300], db[300:600] + 0.125, rng.uniform(-1, 4, (300, 3))])
+    for k in (1, 8, 16, 30):
+        bi, bd = oracle.knn_exact(db, q, k)
+        ti, td = oracle.knn_exact(db, q, k, brute_max_n=0)
+        assert np.array_equal(bi, ti) and np.array_equal(bd, td), k
+    db = rng.uniform(-5, 5, (5000, 3))
+    q = rng.uniform(-5, 5, (500, 3))
+    bi, bd = oracle.knn_exact(db, q, 8)
+    ti, td = oracle.knn_exact(db, q, 8, brute_max_n=0)
+    assert np.array_equal(bi, ti) and np.array_equal(bd, td)
+
+
+def test_radius_exact_matches_bruteforce(oracle):
+    rng = np.random.default_rng(13)
+    for db, q, radii in ((rng.uniform(-5, 5, (3000, 3)), rng.uniform(-5, 5, (30, 3)), (0.0, 0.4, 1.1)),
+                         (_lattice(rng, 3000), None, (0.0, 0.25, 0.5, 1.25))):
+        if q is None:
+            q = np.concatenate([db[:15], db[15:30] + 0.125, db[30:35] + 100.0])
+        for r in radii:
+            offs, idx, dist = oracle.radius_exact(db, q, r)
+            assert offs[0] == 0 and offs[-1] == len(idx) == len(dist)
+            for j in range(len(q)):
+                oi, od = oracle.radius_bruteforce(db, q[j], r)
+                s, e = offs[j], offs[j + 1]
+                assert np.array_equal(idx[s:e], oi) and np.array_equal(dist[s:e], od), (r, j)
+
+
+def test_exact_oracles_match_reference_goldens_outside_ties(oracle):
+    g = load_golden("nn_api.npz")
+    for name, rads in (("rand64", (0.25, 0.5)), ("kitti4000", (0.5, 1.0))):
+        db, qs = g[f"{name}_db"], g[f"{name}_queries"]
+        for k in (1, 8):
+            idx, dist = oracle.knn_exact(db, qs, k)
+            for tree in ("kd", "oct"):
+                gi, gd = g[f"{name}_{tree}_knn{k}_idx"], g[f"{name}_{tree}_knn{k}_dist"]
+                assert np.allclose(dist, gd, rtol=1e-14, atol=0), (name, tree, k)
+                for qi in range(len(qs)):
+                    od = dist[qi]
+                    ok = np.r_[True, od[1:] != od[:-1]] & np.r_[od[:-1] != od[1:], True]
+                    assert np.array_equal(idx[qi][ok], gi[qi][ok]), (name, tree, k, qi)
+        for rad in rads:
+            offs, idx, dist = oracle.radius_exact(db, qs, rad)
+            for qi in range(len(qs)):
+                s, e = offs[qi], offs[qi + 1]
+                for tree in ("kd", "oct", "octfast"):
+                    assert np.array_equal(idx[s:e], g[f"{name}_{tree}_rad{rad}_q{qi}_idx"]), (name, tree, rad, qi)
+                    assert np.allclose(dist[s:e], g[f"{name}_{tree}_rad{rad}_q{qi}_dist"], rtol=1e-14, atol=0)
