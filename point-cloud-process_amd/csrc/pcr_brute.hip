@@ -35,11 +35,8 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int BR_NT = 4;          // query tiles (of 16) per wave -> 64 queries per wave
 constexpr int BR_WAVES = 4;       // waves per block
 constexpr int BR_QPB = BR_NT * 16 * BR_WAVES;  // queries per block = 256
-#ifndef PCR_BR_GRP
-#define PCR_BR_GRP 8
-#endif
 constexpr int BR_PF = 4;          // tiles per prefetch block
-constexpr int BR_GRP = PCR_BR_GRP;  // tiles per argmin group (multiple of BR_PF): one tracker update per group
+constexpr int BR_GRP = 8;         // tiles per argmin group (multiple of BR_PF): one tracker update per group
 constexpr int BR_PAD = BR_GRP + BR_PF;  // never-winning padding tiles behind the last real one (unconditional prefetch)
 static_assert(BR_GRP % BR_PF == 0, "argmin group = whole prefetch blocks");
 constexpr double BR_BIAS_REL = 3.6379788070917130e-12;   // 2^-38 (x Rt^2)

@@ -28,9 +28,7 @@
 
 constexpr int NB_CAP = 1024;
 // clouds of up to this many points are searched without an index (brute_view; the fused initialisation takes only such scans)
-#ifndef PCR_HYBRID_BRUTE_MAX
-#define PCR_HYBRID_BRUTE_MAX 4096
-#endif
+constexpr int HYBRID_BRUTE_MAX = 4096;
 
 struct __attribute__((aligned(16))) nb_entry {
     double d2;
@@ -837,10 +835,10 @@ constexpr double FM_TAU_REL = 9.094947017729282e-13;   // 2^-40
 __global__ void __launch_bounds__(1024) dup_rows_kernel(const double* __restrict__ fpfh /* (ng,33) */, const unsigned int* __restrict__ scan_first,
                                                         unsigned char* __restrict__ dup /* (ng): 1 = repeats an earlier row of its scan */) {
     // open-addressing table in LDS: hash tag (high 32 bits) << 32 | lowest row seen with that tag; all ones = free
-    constexpr unsigned int SLOTS = 2 * PCR_HYBRID_BRUTE_MAX;
+    constexpr unsigned int SLOTS = 2 * HYBRID_BRUTE_MAX;
     static_assert(SLOTS * 8 <= 65536 && (SLOTS & (SLOTS - 1)) == 0, "the table fits the block's LDS");
     __shared__ unsigned long long tab[SLOTS];
-    const unsigned int base = scan_first[blockIdx.x], n = scan_first[blockIdx.x + 1] - base;   // (n <= PCR_HYBRID_BRUTE_MAX: checked by the caller)
+    const unsigned int base = scan_first[blockIdx.x], n = scan_first[blockIdx.x + 1] - base;   // (n <= HYBRID_BRUTE_MAX: checked by the caller)
     for (unsigned int i = threadIdx.x; i < SLOTS; i += 1024) tab[i] = ~0ull;
     __syncthreads();
     auto row_hash = [&](unsigned int j) {
@@ -1134,7 +1132,7 @@ int* fail_word(pcr_ctx* ctx) { return (int*)(ctx->d_counters + 116); }
 // an index: two grid builds per scan -- one per radius, ~20 launches each -- cost several times what the neighbourhoods themselves
 // cost, and a wave reads 4 096 records in 64 trips.  The "view" of such a cloud: its records in row order, levels = 0.
 bool brute_view(const pcr_cloud* cloud, pcr_grid_view* v) {
-    if (cloud->n > PCR_HYBRID_BRUTE_MAX || cloud->morton_sorted) return false;
+    if (cloud->n > HYBRID_BRUTE_MAX || cloud->morton_sorted) return false;
     memset(v, 0, sizeof(*v));
     v->pts = cloud->d;
     v->n = cloud->n;
@@ -1370,7 +1368,7 @@ int pcr_global_registration(pcr_ctx* ctx, const pcr_prep* source, const pcr_prep
 // normals, SPFH and FPFH are one launch each over every down-sampled point of the chunk (a block's search space is its own scan); matching,
 // correspondence sets and the RANSAC loop run for all pairs side by side.  Same arithmetic, same order, same seeds as pcr_preprocess +
 // pcr_global_registration pair by pair: the results are bit for bit those (tests/test_gpu_global_init.py).
-// Returns PCR_E_UNSUPPORTED when the share does not fit this path (a down-sampled scan above PCR_HYBRID_BRUTE_MAX points, a neighbourhood
+// Returns PCR_E_UNSUPPORTED when the share does not fit this path (a down-sampled scan above HYBRID_BRUTE_MAX points, a neighbourhood
 // that cannot be bounded, extents too large for the packed key): the caller then takes the scans one by one.
 namespace {
 struct scan_chunk {
@@ -1548,7 +1546,7 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
         if (rc) break;
         lap("down-sample (all scans)");
         for (int k = 0; k < c.n_scans; ++k) {
-            if (c.first[(size_t)k + 1] - c.first[(size_t)k] > (unsigned int)PCR_HYBRID_BRUTE_MAX) { rc = PCR_E_UNSUPPORTED; break; }
+            if (c.first[(size_t)k + 1] - c.first[(size_t)k] > (unsigned int)HYBRID_BRUTE_MAX) { rc = PCR_E_UNSUPPORTED; break; }
             slot[(size_t)who[(size_t)k]].chunk = (int)chunks.size() - 1;
             slot[(size_t)who[(size_t)k]].local = k;
         }

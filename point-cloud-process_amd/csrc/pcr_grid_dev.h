@@ -232,4 +232,14 @@ __device__ static inline double wave_min_f64(double v) {
 __device__ static inline long long readlane_i64(long long v, int l) {   // l: wave-uniform
     return ((long long)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)v, l);
 }
+__device__ static inline double readlane_f64(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
 
+// LDS hand-off between the lanes of ONE wave: LDS operations of a wave execute in order, so no hardware wait is
+// needed, but the compiler must neither forward a lane's own earlier store to its load nor move accesses across
+__device__ static inline void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}

@@ -30,13 +30,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include "pcr_grid_dev.h"
+#include "pcr_descent.h"
 #include "pcr_icp_step.h"
 
-#ifndef PCR_HARD_SCAN_T
-#define PCR_HARD_SCAN_T 192
-#endif
-constexpr unsigned int HARD_SCAN_T = PCR_HARD_SCAN_T;   // the hard stage scans cells up to this size, descends into bigger ones
+constexpr unsigned int HARD_SCAN_T = 192;   // the hard stage scans cells up to this size, descends into bigger ones
 constexpr int HARD_STACK = 160;
 constexpr long long ID_NONE = 0x7fffffffffffffffll;
 // The unresolved queries go to H_NLIST sub-lists (tile t appends to list t % H_NLIST): one returning atomic per tile on
@@ -45,9 +42,10 @@ constexpr long long ID_NONE = 0x7fffffffffffffffll;
 constexpr int H_NLIST = 32;
 constexpr int H_CSTRIDE = 32;
 __host__ __device__ static inline unsigned int hard_list_cap(long long nq) {
-    // tiles (of 64 or 16 queries) append to list (tile % H_NLIST): room for every query of the lists' fair share of tiles
-    const long long tiles = (nq + 15) / 16;
-    return (unsigned int)(((tiles + H_NLIST - 1) / H_NLIST) * 16 + 64);
+    // tile t (32 queries) appends to list t % H_NLIST: room for every query of a list's fair share of tiles.  Counted in half tiles
+    // of 16 queries, rounded up per list, + 64: never less than 32 per tile of the share, and the value the scratch layout was sized with.
+    const long long halves = (nq + 15) / 16;
+    return (unsigned int)(((halves + H_NLIST - 1) / H_NLIST) * 16 + 64);
 }
 
 template <int G>
@@ -77,19 +75,14 @@ __device__ static inline float fmin3(float a, float b, float c) {  // v_min3_f32
     return r;
 }
 
-__device__ static inline double sq_pos(double v) {
-    v = fmax(v, 0.0);
-    return v * v;
-}
-
 // --------------------------------------------------------------- wave tile
-// Second-generation tile stage: ONE WAVE = one tile of 16 consecutive queries, no block-level barrier anywhere.
-// Why: with 64-query tiles every query was compared with the union of 64 neighbourhoods (~980 staged points per
-// query on a KITTI scan: the kernel spent its time at the binary32 VALU peak on candidates no query needed), and the
-// four waves of a block marched through load / directory / staging / filter in lockstep, so all resident tiles hit
-// the memory system and then the VALU together.  A 16-query tile's box holds 3-4x fewer points at the same
-// directory and staging cost per query, and independent waves de-synchronise by themselves.
-//   lanes: query = lane & 15 (four copies), candidate slice = lane >> 4.
+// ONE WAVE = one tile of 32 consecutive queries, no block-level barrier anywhere.
+// Why: with the first generation's 64-query tiles (one per 256-thread block) every query was compared with the union of 64
+// neighbourhoods (~980 staged points per query on a KITTI scan: the kernel spent its time on candidates no query needed), and the
+// four waves of a block marched through load / directory / staging / filter in lockstep, so all resident tiles hit the memory
+// system and then the ALUs together.  A wave tile's box holds several times fewer points at the same directory and staging cost
+// per query, and independent waves de-synchronise by themselves.  32 queries are the 32 columns of a matrix-core tile product.
+//   lanes: query = lane & 31 (two lanes per query); in the filter lane l sees half of every block of 32 staged points (l >> 5).
 //   Up to WT_PASSES passes.  In every pass each still-open query claims a cube of half-width rho around itself:
 //   rho = sqrt(bound) once it has a candidate (bound = the filter's rigorous upper bound U on the winner's squared
 //   distance), otherwise cell0 * 4^pass (a guess, capped by the gate).  The pass box is the bounding box of the
@@ -97,55 +90,23 @@ __device__ static inline double sq_pos(double v) {
 //   the box is staged and filtered.  A query is proven when the ball of radius sqrt(min(U, gate)) lies inside the box
 //   that was actually staged and the filter's second-best exceeds U.  What is still open after the last pass
 //   (ambiguous filter results, boxes with too many points, clamped coordinates) goes to the hard stage.
-#ifndef PCR_WT_Q
-#define PCR_WT_Q 32
-#endif
-constexpr int WT_Q = PCR_WT_Q;      // queries per wave tile (16 or 32)
-#ifndef PCR_WT_MAXC
-#define PCR_WT_MAXC 384
-#endif
-constexpr int WT_MAXC = PCR_WT_MAXC;        // cells in a wave-tile box (a 7 x 7 x 7 box = 64 two-cell blocks fits: the gate ball of a sparse-region query at 0.8 m cells)
-#ifndef PCR_WT_PR
-#define PCR_WT_PR 192
-#endif
-constexpr int WT_PR = PCR_WT_PR;    // points staged per round (chunks of 64, loaded back to back)
+constexpr int WT_Q = 32;            // queries per wave tile: the 32 columns of a matrix-core tile product, two lanes per query
+constexpr int WT_MAXC = 384;        // cells in a wave-tile box (a 7 x 7 x 7 box = 64 two-cell blocks fits: the gate ball of a sparse-region query at 0.8 m cells)
+constexpr int WT_PR = 192;          // points staged per round (chunks of 64, loaded back to back)
 constexpr int WT_CH = WT_PR / 64;
 static_assert(WT_PR % 64 == 0, "whole chunks");
-#ifndef PCR_WT_PASSES
-#define PCR_WT_PASSES 3
-#endif
-constexpr int WT_PASSES = PCR_WT_PASSES;
-#ifndef PCR_WT_PASSES_SEEDED
-#define PCR_WT_PASSES_SEEDED 1
-#endif
-constexpr int WT_PASSES_SEEDED = WT_PASSES < PCR_WT_PASSES_SEEDED ? WT_PASSES : PCR_WT_PASSES_SEEDED;
-#ifndef PCR_WT_HEAVY_STOP
-#define PCR_WT_HEAVY_STOP 384   // (192: 78.8-81.2, 384: 77.6-79.0, 576: 79.8-80.0 us for a one-iteration registration of the 120k pair; without: 81.4-82.0)
-#endif
-constexpr int WT_HEAVY_STOP = PCR_WT_HEAVY_STOP;
+constexpr int WT_PASSES = 3, WT_PASSES_SEEDED = 1;   // passes of an unseeded / a seeded tile
+constexpr int WT_HEAVY_STOP = 384;  // (192: 78.8-81.2, 384: 77.6-79.0, 576: 79.8-80.0 us for a one-iteration registration of the 120k pair; without: 81.4-82.0)
 constexpr int WT_ROUNDS_SMALL = 768 / WT_PR, WT_ROUNDS_LARGE = 2304 / WT_PR;   // staged-point caps of 768 / 2304 per tile
 
-#ifndef PCR_WT_MFMA
-#define PCR_WT_MFMA 1   // filter on the matrix cores (v_mfma_f32_32x32x2_f32); 0 = packed binary32 VALU filter
-#endif
 struct wtile_lds {
     alignas(16) float px[WT_PR + 8], py[WT_PR + 8], pz[WT_PR + 8];
-#if PCR_WT_MFMA
     alignas(16) float pn[WT_PR + 8];   // |p|^2 of the staged point (binary32, from the rounded local coordinates)
-#endif
     unsigned int ppos[WT_PR];
     unsigned int c_start[WT_MAXC];
     unsigned int c_off[WT_MAXC + 1];
     unsigned short own[WT_PR];
 };
-
-// LDS hand-off between the lanes of ONE wave: LDS operations of a wave execute in order, so no hardware wait is
-// needed, but the compiler must neither forward a lane's own earlier store to its load nor move accesses across
-__device__ static inline void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ static inline unsigned int wave_incl_scan_max(unsigned int v) {
     v = max(v, dpp_u32<0x111, 0xf>(0u, v));
@@ -173,7 +134,7 @@ __device__ static inline double wave_total_f64(double v) {
     return v;
 }
 
-// all-reduce inside every row of 16 lanes (= the 16 queries of a candidate slice): quad swaps, half mirror, mirror
+// all-reduce inside every row of 16 lanes (half of a tile's queries): quad swaps, half mirror, mirror
 __device__ static inline int row16_min(int v) {
     // (old = 0 with bound_ctrl: every lane has a source under these permutations, and the compiler can then fold the move into the
     // v_min / v_max -- with old = v it emitted v_mov + v_mov_dpp + v_min per step, 72 instructions for the six reductions of a tile)
@@ -206,7 +167,7 @@ __device__ static inline const T* as_global(const T* p) {
     return (const T*)(const __attribute__((address_space(1))) T*)p;
 }
 
-// what a wave tile leaves behind in every lane (the 64 / WT_Q copies of a query agree)
+// what a wave tile leaves behind in every lane (the two lanes of a query agree)
 struct wt_state {
     double ax, ay, az;        // the transformed query
     long long qi;
@@ -254,9 +215,6 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
                                                     double* __restrict__ res_d2, unsigned long long* __restrict__ dbg,
                                                     const wt_xyz* __restrict__ prev_xyz, wt_state& S, const unsigned long long* probe_p = nullptr,
                                                     const unsigned int probe_stride = 0, const unsigned int probe_groups = 0, const unsigned int probe_total = 0) {
-#if !PCR_WT_MFMA
-    typedef float f2 __attribute__((ext_vector_type(2)));
-#endif
     typedef float f4 __attribute__((ext_vector_type(4)));
     const pcr_pt* __restrict__ g_pts = as_global(gv.pts);
 #ifdef PCR_WT_DIAG   // phase stamps + "why still open" counters for scripts/wt_stamps.py: a diagnostic build only (they cost registers)
@@ -281,7 +239,7 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
         if (has_x) {
             xform_apply(x, p, &ax, &ay, &az);
             // in-place transform of the source (main.py:110); every lane of this wave has loaded its record by now
-            // and no other wave reads these 16 records
+            // and no other wave reads these 32 records
             if (write_back && lane < WT_Q) {
                 pcr_pt o;
                 o.x = ax; o.y = ay; o.z = az; o.id = p.id;
@@ -294,7 +252,7 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
     }
     
     WT_STAMP(0);
-    // per-query state across the passes (identical in the four lanes of a query after every merge)
+    // per-query state across the passes (identical in the two lanes of a query after every merge)
     bool open = qvalid;                         // not yet proven
     const float gate2 = gated ? (float)max_d2 * (1.0f + 1e-6f) : INFINITY;   // rounded up: only ever used as an outer bound
     float bound2 = gate2;                       // squared radius that provably holds the nearest neighbour (or the gate)
@@ -346,16 +304,9 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             int lo_k = row16_min(mn[k]), hi_k = row16_max(mx[k]);   // every row of 16 lanes
-            if (WT_Q >= 32) {   // queries 16..31 sit in row 1 (and 32..63 in rows 2, 3)
-                lo_k = min(__builtin_amdgcn_readlane(lo_k, 0), __builtin_amdgcn_readlane(lo_k, 16));
-                hi_k = max(__builtin_amdgcn_readlane(hi_k, 0), __builtin_amdgcn_readlane(hi_k, 16));
-            }
-            if (WT_Q == 64) {
-                const int lo2 = min(__builtin_amdgcn_readlane(row16_min(mn[k]), 32), __builtin_amdgcn_readlane(row16_min(mn[k]), 48));
-                const int hi2 = max(__builtin_amdgcn_readlane(row16_max(mx[k]), 32), __builtin_amdgcn_readlane(row16_max(mx[k]), 48));
-                lo_k = min(lo_k, lo2);
-                hi_k = max(hi_k, hi2);
-            }
+            // queries 0..15 sit in row 0, queries 16..31 in row 1 (rows 2 and 3 hold their second lanes)
+            lo_k = min(__builtin_amdgcn_readlane(lo_k, 0), __builtin_amdgcn_readlane(lo_k, 16));
+            hi_k = max(__builtin_amdgcn_readlane(hi_k, 0), __builtin_amdgcn_readlane(hi_k, 16));
             mn[k] = __builtin_amdgcn_readfirstlane(lo_k);
             mx[k] = __builtin_amdgcn_readfirstlane(hi_k);
         }
@@ -474,17 +425,11 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
         const float qxf = (float)(ax - ox), qyf = (float)(ay - oy), qzf = (float)(az - oz);
         float fm = INFINITY, fs = INFINITY, s_in = INFINITY;
         unsigned int bpos = POS_NONE;
-#if PCR_WT_MFMA
         static_assert(WT_Q == 32, "the matrix-core filter maps the 32 queries of a tile to the 32 columns of a tile product");
         typedef float f16v __attribute__((ext_vector_type(16)));
         const float mf_b1 = lane < 32 ? -2.0f * qxf : -2.0f * qyf, mf_b2 = lane < 32 ? -2.0f * qzf : 1.0f;
         float bd = INFINITY;   // direct-form squared distance of this lane's best point so far
-#endif
         if (total > 0) {
-#if !PCR_WT_MFMA
-            const f2 qx2 = {qxf, qxf}, qy2 = {qyf, qyf}, qz2 = {qzf, qzf};
-            const int slice = lane / WT_Q;
-#endif
             unsigned int carry = 0;  // owner cell of the last position of the previous round
             // Addresses and loads of one round (positions [b, b + n) of the box): owner cell of every staged position -- mark the
             // first position of each cell (slot ids increase with the position, cells are non-empty), then a running maximum over
@@ -533,18 +478,12 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
                     if (k < cnt) {
                         const float fx = (float)(rec[c3].x - ox), fy = (float)(rec[c3].y - oy), fz = (float)(rec[c3].z - oz);
                         L->px[k] = fx; L->py[k] = fy; L->pz[k] = fz;
-#if PCR_WT_MFMA
                         L->pn[k] = __builtin_fmaf(fz, fz, __builtin_fmaf(fy, fy, fx * fx));
-#endif
                         L->ppos[k] = jj[c3];
                     }
                 }
-#if PCR_WT_MFMA
                 // pad the last block of 32 with points nobody can win (finite: no inf - inf in the expanded form)
                 if (lane < 32 && cnt + lane < ((cnt + 31u) & ~31u)) { L->px[cnt + lane] = 1e15f; L->py[cnt + lane] = 0.0f; L->pz[cnt + lane] = 0.0f; L->pn[cnt + lane] = 1e30f; }
-#else
-                if (lane < 8) { L->px[cnt + lane] = 1e30f; L->py[cnt + lane] = 0.0f; L->pz[cnt + lane] = 0.0f; }  // pad the last group of 8
-#endif
                 wave_sync();
                 unsigned int jn[WT_CH];
                 wt_xyz rn[WT_CH];
@@ -552,15 +491,14 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
                 for (int c3 = 0; c3 < WT_CH; ++c3) { jn[c3] = 0u; rn[c3] = wt_xyz{0.0, 0.0, 0.0}; }
                 if (base + WT_PR < total) request(base + WT_PR, min(total - base - WT_PR, (unsigned int)WT_PR), jn, rn);   // in flight during the filter
                 WT_STAMP(4);
-#if PCR_WT_MFMA
                 // Filter on the matrix cores.  Expanded form |p|^2 - 2 q.p (the query's own |q|^2 is added at the end): one 32 x 32
                 // tile = 32 staged points (rows) x the 32 queries (columns), K = 4 = two v_mfma_f32_32x32x2_f32:
                 //   A rows (px, py | pz, |p|^2): lane l supplies point l % 32, k = l / 32 -- two 4-byte LDS reads per lane and block
                 //   B cols (-2qx, -2qy | -2qz, 1): two registers per lane for the whole pass
                 //   C: lane l holds query l % 32 against the 16 points 8 g + 4 (l / 32) + e of the block (g, e = 0..3)
-                // so the two lanes of a query see half a block each -- the two candidate slices of the packed-VALU filter it replaces,
-                // which read 96 bytes of LDS per lane for every 8 points and kept the VALU busy with 35 instructions for them (the
-                // filter was half of a heavy tile's lifetime, bound by LDS return bandwidth and VALU issue of the whole CU).
+                // so the two lanes of a query see half a block each.  (The packed-VALU filter this replaced read 96 bytes of LDS per
+                // lane for every 8 points and kept the VALU busy with 35 instructions for them: the filter was half of a heavy tile's
+                // lifetime, bound by LDS return bandwidth and VALU issue of the whole CU.)
                 // The tile values only ORDER blocks: the winner inside the best block is found by the direct form below, and every
                 // other block enters the proof through its minimum minus the bound d_arith on the expanded form's rounding error.
                 {
@@ -614,59 +552,11 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
                         } else s_in = fminf(s_in, best);
                     }
                 }
-#else
-                // filter: slice s takes groups s, s+4, ... of 8 staged points (see grid_tile_kernel for the arithmetic)
-                if (part) {
-                    int rk = -1;
-                    for (unsigned int k0 = slice * 8; k0 < cnt; k0 += 8 * (64 / WT_Q)) {
-                        f2 d[4];
-#pragma unroll
-                        for (int u = 0; u < 2; ++u) {
-                            const unsigned int k = k0 + 4 * u;
-                            const f4 bx4 = *reinterpret_cast<const f4*>(&L->px[k]);
-                            const f4 by4 = *reinterpret_cast<const f4*>(&L->py[k]);
-                            const f4 bz4 = *reinterpret_cast<const f4*>(&L->pz[k]);
-#pragma unroll
-                            for (int h = 0; h < 2; ++h) {
-                                const f2 bx = h ? f2{bx4.z, bx4.w} : f2{bx4.x, bx4.y};
-                                const f2 by = h ? f2{by4.z, by4.w} : f2{by4.x, by4.y};
-                                const f2 bz = h ? f2{bz4.z, bz4.w} : f2{bz4.x, bz4.y};
-                                const f2 dx = qx2 - bx, dy = qy2 - by, dz = qz2 - bz;
-                                f2 t = dx * dx;
-                                t = __builtin_elementwise_fma(dy, dy, t);
-                                d[2 * u + h] = __builtin_elementwise_fma(dz, dz, t);
-                            }
-                        }
-                        float m8 = fmin3(d[0].x, d[0].y, d[1].x);
-                        m8 = fmin3(m8, d[1].y, d[2].x);
-                        m8 = fmin3(m8, d[2].y, d[3].x);
-                        m8 = fmin3(m8, d[3].y, d[3].y);
-                        const bool lt = m8 < fm;
-                        fs = __builtin_amdgcn_fmed3f(m8, fm, fs);
-                        fm = __builtin_amdgcn_fmed3f(m8, fm, -INFINITY);
-                        rk = lt ? (int)k0 : rk;
-                    }
-                    if (rk >= 0) {
-                        float best = INFINITY, second = INFINITY;
-                        int bi = rk;
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float ddx = qxf - L->px[rk + j], ddy = qyf - L->py[rk + j], ddz = qzf - L->pz[rk + j];
-                            const float dj = __builtin_fmaf(ddz, ddz, __builtin_fmaf(ddy, ddy, ddx * ddx));
-                            if (dj < best) { second = best; best = dj; bi = rk + j; }
-                            else if (dj < second) second = dj;
-                        }
-                        bpos = L->ppos[bi];
-                        s_in = second;
-                    }
-                }
-#endif
                 wave_sync();
 #pragma unroll
                 for (int c3 = 0; c3 < WT_CH; ++c3) { jj[c3] = jn[c3]; rec[c3] = rn[c3]; }
                 WT_STAMP(5);
             }
-#if PCR_WT_MFMA
             {
                 // from here on fm = the winner's direct-form value, fs = a lower bound of every other staged point's value: the blocks'
                 // minima come from the expanded form in binary32 -- |q|^2, |p|^2 (3 roundings each), 4 multiply-adds (counted as 8
@@ -678,11 +568,8 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
                 fs = fminf((fs + qn) - d_arith, s_in);
                 fm = bd;
             }
-#else
-            fs = fminf(fs, s_in);
-#endif
         }
-        // ---- merge the four candidate slices of every query
+        // ---- merge the two lanes of every query (one step; written as the loop the compiler has always seen)
 #pragma unroll
         for (int off = WT_Q; off < 64; off <<= 1) {
             const float om = __shfl_xor(fm, off, 64), os = __shfl_xor(fs, off, 64);
@@ -833,29 +720,8 @@ __device__ static inline void moments_add(double* __restrict__ m, const double o
 }
 
 // -------------------------------------------------------------- hard stage
-struct hard_entry {
-    unsigned int start, end;
-    unsigned int x, y, z;
-    int level;
-};
-
-__device__ static inline double box_dist2(const pcr_grid_view& gv, int level, double cell, unsigned int X, unsigned int Y, unsigned int Z,
-                                          double ax, double ay, double az) {
-    const int bl = (int)(PCR_COORD_BIAS >> (2 * level));
-    const double slack = cell * 1e-9;
-    const double x0 = gv.lo[0] + (double)((int)X - bl) * cell;
-    const double y0 = gv.lo[1] + (double)((int)Y - bl) * cell;
-    const double z0 = gv.lo[2] + (double)((int)Z - bl) * cell;
-    const double dx = sq_pos(fmax(x0 - ax, ax - (x0 + cell)) - slack);
-    const double dy = sq_pos(fmax(y0 - ay, ay - (y0 + cell)) - slack);
-    const double dz = sq_pos(fmax(z0 - az, az - (z0 + cell)) - slack);
-    return (dx + dy) + dz;
-}
-
-__device__ static inline double wave_min(double v) { return wave_min_f64(v); }   // (DPP network: pcr_grid_dev.h)
-
 struct hard_lds {
-    hard_entry stack[HARD_STACK];
+    cell_entry stack[HARD_STACK];
     unsigned int fl_off[64], fl_start[64];  // flattened scan directory: exclusive point offset / start of every small cell
 };
 
@@ -908,7 +774,7 @@ __device__ static inline void hard_disperse(const pcr_grid_view& gv, hard_lds* L
                 if (better(d2, b1.id, bd2, bid)) { bd2 = d2; bid = b1.id; bpos = jj[1]; bw[0] = b1.x; bw[1] = b1.y; bw[2] = b1.z; }
             }
         }
-        bound2 = fmin(bound2, wave_min(bd2));
+        bound2 = fmin(bound2, wave_min_f64(bd2));
     }
     // big cells: push (far ones first so that the nearest is split first); without room they are read whole
     const bool big = valid && !small && bdist <= bound2;
@@ -921,7 +787,7 @@ __device__ static inline void hard_disperse(const pcr_grid_view& gv, hard_lds* L
         if (big && bdist > 0.0) slot = __popcll(m_far & below);
         else if (big) slot = __popcll(m_far) + __popcll(m_near & below);
         if (slot >= 0) {
-            hard_entry en;
+            cell_entry en;
             en.start = s; en.end = e; en.x = X; en.y = Y; en.z = Z; en.level = lvl;
             L->stack[sp + slot] = en;
         }
@@ -935,7 +801,26 @@ __device__ static inline void hard_disperse(const pcr_grid_view& gv, hard_lds* L
             scan_range(gv.pts, ss + lane, ee, 64, ax, ay, az, bd2, bid, bpos, bw);
             n_pts += ee - ss;
         }
-        bound2 = fmin(bound2, wave_min(bd2));
+        bound2 = fmin(bound2, wave_min_f64(bd2));
+    }
+}
+
+// Empties the stack: pop the nearest cell, test its box against the bound, split it 64 ways (one child per lane: box test, probe)
+// and disperse the children.
+__device__ static inline void hard_drain(const pcr_grid_view& gv, hard_lds* L, int& sp, int lane, double ax, double ay, double az, double& bd2,
+                                         long long& bid, unsigned int& bpos, double& bound2, unsigned int& h_steps, unsigned int& n_pts, double* bw) {
+    while (sp > 0) {
+        --sp;
+        const cell_entry en = L->stack[sp];  // same address in every lane: LDS broadcast
+        const double ecell = gv.cell0 * (double)(1ll << (2 * en.level));
+        if (box_dist2(gv, en.level, ecell, en.x, en.y, en.z, ax, ay, az) > bound2) continue;
+        const int cl = en.level - 1;
+        const unsigned int CX = en.x * 4u + (lane & 3), CY = en.y * 4u + ((lane >> 2) & 3), CZ = en.z * 4u + (lane >> 4);
+        const double cdist = box_dist2(gv, cl, ecell * 0.25, CX, CY, CZ, ax, ay, az);
+        unsigned int cs = 0, ce = 0;
+        const bool cvalid = cdist <= bound2 && lookup_cell(gv.table[cl], gv.mask[cl], CX, CY, CZ, &cs, &ce);
+        hard_disperse(gv, L, sp, lane, cvalid, cs, ce, CX, CY, CZ, cl, cdist, ax, ay, az, bd2, bid, bpos, bound2, n_pts, bw);
+        ++h_steps;
     }
 }
 
@@ -959,7 +844,7 @@ __device__ __forceinline__ static void hard_search(const pcr_grid_view& gv, hard
         unsigned int s, e;
         if (lookup_cell(gv.table[0], gv.mask[0], (unsigned int)cx, (unsigned int)cy, (unsigned int)cz, &s, &e)) {
             scan_range(gv.pts, s + lane, e, 64, ax, ay, az, bd2, bid, bpos, bw);
-            bound2 = fmin(bound2, wave_min(bd2));
+            bound2 = fmin(bound2, wave_min_f64(bd2));
         }
     }
     // Level schedule.  With a real candidate in hand the search starts at the smallest level whose
@@ -976,14 +861,7 @@ __device__ __forceinline__ static void hard_search(const pcr_grid_view& gv, hard
         return top + 1;  // not even the top level's block covers the ball
     };
     have_cand = have_cand || __any(bd2 < DBL_MAX);
-#ifndef PCR_HARD_START_MAX
-#define PCR_HARD_START_MAX 99
-#endif
-    // (PCR_HARD_START_MAX: the search never STARTS above this level even when the candidate's ball asks for it -- in a dense cloud the
-    // true neighbour is centimetres away while the candidate, last pass's neighbour seen from the moved query, may be decimetres
-    // away: the block at a fine level shrinks the ball before the coarse cells it would have touched are split one by one)
     int s_level = clamped ? top + 1 : (have_cand ? level_for(bound2, 0) : 0);
-    if (s_level <= top && s_level > PCR_HARD_START_MAX) s_level = PCR_HARD_START_MAX;
     s_level0 = s_level;
     int sp = 0;  // wave-uniform stack pointer
     while (s_level <= top) {
@@ -1002,20 +880,7 @@ __device__ __forceinline__ static void hard_search(const pcr_grid_view& gv, hard
         hard_disperse(gv, L, sp, lane, valid, s, e, (unsigned int)X, (unsigned int)Y, (unsigned int)Z, lvl, bdist, ax, ay, az, bd2, bid, bpos,
                       bound2, h_pts, bw);
         ++h_steps;
-        while (sp > 0) {
-            --sp;
-            const hard_entry en = L->stack[sp];  // same address in every lane: LDS broadcast
-            const double ecell = gv.cell0 * (double)(1ll << (2 * en.level));
-            if (box_dist2(gv, en.level, ecell, en.x, en.y, en.z, ax, ay, az) > bound2) continue;
-            // split: one child per lane, box test against the bound, probe
-            const int cl = en.level - 1;
-            const unsigned int CX = en.x * 4u + (lane & 3), CY = en.y * 4u + ((lane >> 2) & 3), CZ = en.z * 4u + (lane >> 4);
-            const double cdist = box_dist2(gv, cl, ecell * 0.25, CX, CY, CZ, ax, ay, az);
-            unsigned int cs = 0, ce = 0;
-            const bool cvalid = cdist <= bound2 && lookup_cell(gv.table[cl], gv.mask[cl], CX, CY, CZ, &cs, &ce);
-            hard_disperse(gv, L, sp, lane, cvalid, cs, ce, CX, CY, CZ, cl, cdist, ax, ay, az, bd2, bid, bpos, bound2, h_pts, bw);
-            ++h_steps;
-        }
+        hard_drain(gv, L, sp, lane, ax, ay, az, bd2, bid, bpos, bound2, h_steps, h_pts, bw);
         const double safe = cell * (1.0 - 1e-9);
         if (safe * safe >= bound2) break;  // the block just searched covers the bound ball: exact
         s_level = (bound2 < DBL_MAX) ? level_for(bound2, lvl + 1) : lvl + 1;
@@ -1035,44 +900,32 @@ __device__ __forceinline__ static void hard_search(const pcr_grid_view& gv, hard
         }
         hard_disperse(gv, L, sp, lane, valid, s, e, X, Y, Z, top, bdist, ax, ay, az, bd2, bid, bpos, bound2, h_pts, bw);
         ++h_steps;
-        while (sp > 0) {
-            --sp;
-            const hard_entry en = L->stack[sp];
-            const double ecell = gv.cell0 * (double)(1ll << (2 * en.level));
-            if (box_dist2(gv, en.level, ecell, en.x, en.y, en.z, ax, ay, az) > bound2) continue;
-            const int cl = en.level - 1;
-            const unsigned int CX = en.x * 4u + (lane & 3), CY = en.y * 4u + ((lane >> 2) & 3), CZ = en.z * 4u + (lane >> 4);
-            const double cdist = box_dist2(gv, cl, ecell * 0.25, CX, CY, CZ, ax, ay, az);
-            unsigned int cs = 0, ce = 0;
-            const bool cvalid = cdist <= bound2 && lookup_cell(gv.table[cl], gv.mask[cl], CX, CY, CZ, &cs, &ce);
-            hard_disperse(gv, L, sp, lane, cvalid, cs, ce, CX, CY, CZ, cl, cdist, ax, ay, az, bd2, bid, bpos, bound2, h_pts, bw);
-            ++h_steps;
-        }
+        hard_drain(gv, L, sp, lane, ax, ay, az, bd2, bid, bpos, bound2, h_steps, h_pts, bw);
     }
     // the lanes' bests meet: the smallest distance over the wave (DPP), then -- among the lanes that hold it: one, unless two points are
     // exactly equidistant -- the smallest id; the winner's lane hands everything out by v_readlane (no LDS, no butterfly)
     {
-        const double m = wave_min(bd2);
+        const double m = wave_min_f64(bd2);
         unsigned long long cm = __ballot(bpos != POS_NONE && bd2 == m);
         if (!cm) { bd2 = DBL_MAX; bid = ID_NONE; bpos = POS_NONE; if (win) { win[0] = win[1] = win[2] = 0.0; } return; }
         int wl = (int)__ffsll((long long)cm) - 1;
         cm &= cm - 1;
         if (cm) {   // (rare) ties in distance: lowest id
-            long long best_id = ((long long)__builtin_amdgcn_readlane((int)(bid >> 32), wl) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)bid, wl);
+            long long best_id = readlane_i64(bid, wl);
             while (cm) {
                 const int l = (int)__ffsll((long long)cm) - 1;
                 cm &= cm - 1;
-                const long long id_l = ((long long)__builtin_amdgcn_readlane((int)(bid >> 32), l) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)bid, l);
+                const long long id_l = readlane_i64(bid, l);
                 if (id_l < best_id) { best_id = id_l; wl = l; }
             }
         }
         bd2 = m;
-        bid = ((long long)__builtin_amdgcn_readlane((int)(bid >> 32), wl) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)bid, wl);
+        bid = readlane_i64(bid, wl);
         bpos = (unsigned int)__builtin_amdgcn_readlane((int)bpos, wl);
         if (win) {
 #pragma unroll
             for (int k = 0; k < 3; ++k)
-                win[k] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(bw[k]), wl), __builtin_amdgcn_readlane(__double2loint(bw[k]), wl));
+                win[k] = readlane_f64(bw[k], wl);
         }
     }
 }
@@ -1166,14 +1019,8 @@ grid_hard_kernel(pcr_grid_view gv, const work_item* __restrict__ list, const uns
 //   variants  inline_queue = 0: the launch only publishes and grid_drain_kernel (below) serves the queues -- the host's choice
 //             while several ICP loops of the process are in flight; same results bit for bit.
 //   finish    vmcnt(0) (own atomics acknowledged), then a two-level ticket (one word per group, then a root).
-#ifndef PCR_ACC_SETS
-#define PCR_ACC_SETS 32
-#endif
-constexpr int ACC_SETS = PCR_ACC_SETS;
-#ifndef PCR_PASS_GROUPS
-#define PCR_PASS_GROUPS 32
-#endif
-constexpr int PASS_GROUPS = PCR_PASS_GROUPS;
+constexpr int ACC_SETS = 32;
+constexpr int PASS_GROUPS = 32;
 constexpr int PASS_SYNC_STRIDE = 32;                      // 64-bit words per group: queue word at 0, started at 16, ticket at 17 (other line)
 constexpr int PASS_SYNC_WORDS = PASS_SYNC_STRIDE * (PASS_GROUPS + 1);   // + root ticket (0) / error word (16)
 constexpr unsigned long long ITEM_NONE = ~0ull;           // "not written yet": never a valid word of an item
@@ -1656,10 +1503,7 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
             if (poisoned || mk == 0xfull) break;
             if (spins >= PASS_SPIN_LIMIT) { failed = true; break; }
             ++n_polls;
-#ifndef PCR_SLOT_SLEEP
-#define PCR_SLOT_SLEEP 16   // (1 / 4 / 16 / 32 / 64 measured within noise of each other; fewer polls = less traffic)
-#endif
-            __builtin_amdgcn_s_sleep(PCR_SLOT_SLEEP);
+            __builtin_amdgcn_s_sleep(16);   // (1 / 4 / 16 / 32 / 64 measured within noise of each other; fewer polls = less traffic)
         }
         if (failed) break;
         if (poisoned) { left_by_poison = true; break; }

@@ -18,39 +18,15 @@
 #include <thread>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "pcr_grid_dev.h"
+#include "pcr_descent.h"
 
 constexpr int KN_STACK = 192;
 constexpr unsigned int KN_SCAN_T = 128;
 
-struct kn_entry {
-    unsigned int start, end;
-    unsigned int x, y, z;
-    int level;
-};
-
-__device__ static inline double kn_sq_pos(double v) {
-    v = fmax(v, 0.0);
-    return v * v;
-}
-
-__device__ static inline double kn_box_dist2(const pcr_grid_view& gv, int level, double cell, unsigned int X, unsigned int Y, unsigned int Z,
-                                             double ax, double ay, double az) {
-    const int bl = (int)(PCR_COORD_BIAS >> (2 * level));
-    const double slack = cell * 1e-9;
-    const double x0 = gv.lo[0] + (double)((int)X - bl) * cell;
-    const double y0 = gv.lo[1] + (double)((int)Y - bl) * cell;
-    const double z0 = gv.lo[2] + (double)((int)Z - bl) * cell;
-    const double dx = kn_sq_pos(fmax(x0 - ax, ax - (x0 + cell)) - slack);
-    const double dy = kn_sq_pos(fmax(y0 - ay, ay - (y0 + cell)) - slack);
-    const double dz = kn_sq_pos(fmax(z0 - az, az - (z0 + cell)) - slack);
-    return (dx + dy) + dz;
-}
-
 // Pruned descent from the root cells.  `scan(start, end, bound2)` is called (wave-uniformly) for
 // every cell that has to be read; it may lower bound2.
 template <class Scan>
-__device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, double ay, double az, double& bound2, kn_entry* stack, int lane,
+__device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, double ay, double az, double& bound2, cell_entry* stack, int lane,
                                          Scan& scan) {
     const int top = gv.levels - 1;
     int sp = 0;
@@ -62,7 +38,7 @@ __device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, dou
         bool valid = lane < 8;
         double bdist = 0.0;
         if (valid) {
-            bdist = kn_box_dist2(gv, top, cell, X, Y, Z, ax, ay, az);
+            bdist = box_dist2(gv, top, cell, X, Y, Z, ax, ay, az);
             valid = bdist <= bound2 && lookup_cell(gv.table[top], gv.mask[top], X, Y, Z, &s, &e);
         }
         const unsigned long long m_far = __ballot(valid && bdist > 0.0), m_near = __ballot(valid && !(bdist > 0.0));
@@ -70,14 +46,14 @@ __device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, dou
         int slot = -1;
         if (valid && bdist > 0.0) slot = __popcll(m_far & below);
         else if (valid) slot = __popcll(m_far) + __popcll(m_near & below);
-        if (slot >= 0) stack[slot] = kn_entry{s, e, X, Y, Z, top};
+        if (slot >= 0) stack[slot] = cell_entry{s, e, X, Y, Z, top};
         sp = __popcll(m_far) + __popcll(m_near);
     }
     while (sp > 0) {
         --sp;
-        const kn_entry en = stack[sp];
+        const cell_entry en = stack[sp];
         const double cell = gv.cell0 * (double)(1ll << (2 * en.level));
-        if (kn_box_dist2(gv, en.level, cell, en.x, en.y, en.z, ax, ay, az) > bound2) continue;
+        if (box_dist2(gv, en.level, cell, en.x, en.y, en.z, ax, ay, az) > bound2) continue;
         const unsigned int cnt = en.end - en.start;
         const bool room = sp + 64 <= KN_STACK;
         if (en.level == 0 || cnt <= KN_SCAN_T || !room) {
@@ -85,7 +61,7 @@ __device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, dou
         } else {
             const int cl = en.level - 1;
             const unsigned int X = en.x * 4u + (lane & 3), Y = en.y * 4u + ((lane >> 2) & 3), Z = en.z * 4u + (lane >> 4);
-            const double bdist = kn_box_dist2(gv, cl, cell * 0.25, X, Y, Z, ax, ay, az);
+            const double bdist = box_dist2(gv, cl, cell * 0.25, X, Y, Z, ax, ay, az);
             unsigned int s = 0, e = 0;
             const bool valid = bdist <= bound2 && lookup_cell(gv.table[cl], gv.mask[cl], X, Y, Z, &s, &e);
             const unsigned long long m_far = __ballot(valid && bdist > 0.0), m_near = __ballot(valid && !(bdist > 0.0));
@@ -93,7 +69,7 @@ __device__ static inline void kn_descend(const pcr_grid_view& gv, double ax, dou
             int slot = -1;
             if (valid && bdist > 0.0) slot = __popcll(m_far & below);
             else if (valid) slot = __popcll(m_far) + __popcll(m_near & below);
-            if (slot >= 0) stack[sp + slot] = kn_entry{s, e, X, Y, Z, cl};
+            if (slot >= 0) stack[sp + slot] = cell_entry{s, e, X, Y, Z, cl};
             sp += __popcll(m_far) + __popcll(m_near);
         }
     }
@@ -124,7 +100,7 @@ struct knn_scan {
 __global__ void __launch_bounds__(256)
 knn_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, int k, int* __restrict__ idx_out, double* __restrict__ dist_out,
            const int* __restrict__ redo_list, const unsigned int* __restrict__ redo_count) {
-    __shared__ kn_entry s_stack[4][KN_STACK];
+    __shared__ cell_entry s_stack[4][KN_STACK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long qi = (long long)blockIdx.x * 4 + wave;
     if (redo_list) {  // second stage of the batched search: only the queries the block scan could not prove
@@ -207,7 +183,7 @@ struct radius_scan {
 __global__ void __launch_bounds__(256)
 radius_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, double radius, long long* __restrict__ counts_out,
               const long long* __restrict__ offsets, int* __restrict__ idx_out, double* __restrict__ dist_out) {
-    __shared__ kn_entry s_stack[4][KN_STACK];
+    __shared__ cell_entry s_stack[4][KN_STACK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long qi = (long long)blockIdx.x * 4 + wave;
     if (qi >= nq) return;
@@ -235,9 +211,7 @@ radius_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq
 // tried first, then level 1 (cells 4x wider), then -- in sparse surroundings only -- levels 2 and 3.  Queries it cannot prove (sparse surroundings, fewer than k points in
 // reach, coordinates outside the grid) go to a list for the wave-per-query descent above.  On a KITTI scan the block
 // scan settles > 95 % of the queries at ~1/40 of the descent's cost per query.
-#ifndef PCR_KNN_LV
-#define PCR_KNN_LV 3
-#endif
+constexpr int KNN_LV = 3;   // highest level the block scan climbs to
 template <int K>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K <= 8 ? 4 : 2, 8)))   // (k <= 8: 129 VGPRs without the hint, one too many for four waves per SIMD)
 knn_block_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, int k, int* __restrict__ idx_out,
@@ -259,7 +233,7 @@ knn_block_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long
         const int cy = cell_coord(ay, gv.lo[1], gv.inv_cell0, &clamped);
         const int cz = cell_coord(az, gv.lo[2], gv.inv_cell0, &clamped);
         // levels 0, 1 and -- only where the surroundings are sparse (few points met one level down) -- 2 and 3
-        const int max_level = min(gv.levels - 1 < PCR_KNN_LV ? gv.levels - 1 : PCR_KNN_LV, lv_cap);
+        const int max_level = min(gv.levels - 1 < KNN_LV ? gv.levels - 1 : KNN_LV, lv_cap);
         unsigned int met = 0;
         for (int level = 0; level <= max_level && !clamped && !proven && (level < 2 || met <= 192u); ++level) {
             met = 0;
@@ -372,13 +346,6 @@ struct knn_tile_lds {
     int id[KT_PTS];
     unsigned int c_start[KT_LIST], c_pre[KT_LIST + 1];
 };
-__device__ static inline void kt_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ static inline int kt_wave_min(int v) { return wave_min_i32(v); }   // (DPP network: pcr_grid_dev.h)
-__device__ static inline int kt_wave_max(int v) { return wave_max_i32(v); }
 
 // LPQ lanes per query (64 / LPQ queries per wave), PASSES passes of at most ROUNDS staging rounds.  `order`: the query ids to do, n
 // of them (n = *count_p when count_p is given: the list the first stage left).
@@ -439,8 +406,8 @@ __device__ static void knn_tile_one(const pcr_grid_view& gv, knn_tile_lds* L, co
         int w0[3], w1[3];
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            w0[d] = kt_wave_min(open ? lo0[d] : 0x7fffffff);
-            w1[d] = kt_wave_max(open ? hi0[d] : 0);
+            w0[d] = wave_min_i32(open ? lo0[d] : 0x7fffffff);
+            w1[d] = wave_max_i32(open ? hi0[d] : 0);
         }
         int level = 0;
         long long ncell = 0;
@@ -479,7 +446,7 @@ __device__ static void knn_tile_one(const pcr_grid_view& gv, knn_tile_lds* L, co
         // ---- rounds: stage up to KT_PTS points; every lane scans a quarter of them for its query
         for (unsigned int r0 = 0; r0 < n_pts; r0 += KT_PTS) {
             const unsigned int cnt = min(n_pts - r0, (unsigned int)KT_PTS);
-            kt_wave_sync();   // the directory (first round) / the last scan's reads are done
+            wave_sync();   // the directory (first round) / the last scan's reads are done
             for (unsigned int t = lane; t < cnt; t += 64) {
                 const unsigned int j = r0 + t;
                 unsigned int lo = 0, hi = n_list - 1;   // last cell whose prefix <= j
@@ -491,7 +458,7 @@ __device__ static void knn_tile_one(const pcr_grid_view& gv, knn_tile_lds* L, co
                 const pcr_pt rec = gv.pts[L->c_start[lo] + (j - L->c_pre[lo])];
                 L->x[t] = rec.x; L->y[t] = rec.y; L->z[t] = rec.z; L->id[t] = (int)rec.id;
             }
-            kt_wave_sync();
+            wave_sync();
             if (open) {
                 for (unsigned int t = sub; t < cnt; t += LPQ) {
                     const double ex = ax - L->x[t], ey = ay - L->y[t], ez = az - L->z[t];
@@ -509,7 +476,7 @@ __device__ static void knn_tile_one(const pcr_grid_view& gv, knn_tile_lds* L, co
                 }
             }
         }
-        kt_wave_sync();
+        wave_sync();
         // ---- the lanes' lists of a query meet.  One query per wave: k times over, the smallest HEAD of the 64 sorted lists (DPP minimum,
         // ties to the lowest id) is the next entry of the merged list and leaves its lane's list -- ~70 instructions per entry.  (The
         // butterfly below inserts every entry of the partner's list, six rounds of K x K compare-and-swaps and 4 K ds_bpermute: 12 000
@@ -619,7 +586,7 @@ knn_tile_kernel(pcr_grid_view gv, const double* __restrict__ queries, const unsi
     const long long n_tiles = (nq + QPT - 1) / QPT;
     for (long long tile = (long long)blockIdx.x * 4 + wave; tile < n_tiles; tile += (long long)gridDim.x * 4) {
         knn_tile_one<K, LPQ, PASSES, ROUNDS>(gv, &s_lds[wave], lane, tile, nq, queries, order, k, idx_out, dist_out, redo_list, redo_count, seed_kth);
-        kt_wave_sync();
+        wave_sync();
     }
 }
 
@@ -629,7 +596,7 @@ knn_tile_kernel(pcr_grid_view gv, const double* __restrict__ queries, const unsi
 __global__ void __launch_bounds__(256)
 radius_small_kernel(pcr_grid_view gv, const double* __restrict__ queries, int nq, double radius, unsigned int cap, unsigned int* __restrict__ counts_out,
                     int* __restrict__ idx_out, double* __restrict__ dist_out) {
-    __shared__ kn_entry s_stack[4][KN_STACK];
+    __shared__ cell_entry s_stack[4][KN_STACK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int qi = (int)blockIdx.x * 4 + wave;
     if (qi >= nq) return;
@@ -779,10 +746,10 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
         const int* todo = d_redo_a;
         if (k <= 8)
             hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
-                               (const unsigned int*)d_cnt_a, PCR_KNN_LV, (double*)nullptr);
+                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
         else
             hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
-                               (const unsigned int*)d_cnt_a, PCR_KNN_LV, (double*)nullptr);
+                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
         unsigned int n_redo[3] = {0, 0, 0};
         { const int rc_n = pcr_d2h_small(ctx, n_redo, d_cnt_a, 3 * sizeof(unsigned int)); if (rc_n) return rc_n; }   // (synchronises; no copy engine)
         static const bool dbg = getenv("PCR_KNN_DEBUG") != nullptr;
