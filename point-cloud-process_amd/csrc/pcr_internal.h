@@ -186,6 +186,7 @@ struct pcr_dev_block {
     pcr_dev_block& operator=(const pcr_dev_block&) = delete;
     int alloc(size_t b) { free_now(); bytes = b; return pcr_dev_alloc(ctx, b, &p); }
     void free_now() { if (p) pcr_dev_free(ctx, p, bytes); p = nullptr; bytes = 0; }
+    void adopt(void* q, size_t b) { free_now(); p = q; bytes = b; }   // a block somebody else took from the arena
     ~pcr_dev_block() { free_now(); }
     template <typename T> T* as() const { return (T*)p; }
 };
@@ -257,7 +258,7 @@ PCR_HIDDEN int pcr_d2h_staged(pcr_ctx* ctx, void* host_dst, const void* dev_src,
 // (scans[s].first_pt .. + n_pts; mn / mx = the scan's bounding box).  Out, from the arena (the caller frees: sizes ng, ng, n_scans + 1):
 // the records by row WITHIN their scan, the scan of every record, the first record of every scan (+ the total) -- the latter also on the host.
 struct pcr_down_scan { unsigned int first_pt, n_pts; double mn[3], mx[3]; };
-// prepare_dataset + execute_global_registration for a share of pairs at once (pcr_fpfh.hip): scans[] = rows of clouds[] that a pair of todo[] uses;
+// prepare_dataset + execute_global_registration for a share of pairs at once (pcr_global_init.hip): scans[] = rows of clouds[] that a pair of todo[] uses;
 // T_init (16 doubles per row of pairs[]) gets the result of every pair with a valid hypothesis.  PCR_E_UNSUPPORTED: take the scans one by one.
 PCR_HIDDEN int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_clouds, const int64_t* scans, int64_t n_scans, const pcr_pair_ref* pairs,
                                      const int64_t* todo, int64_t n_todo, const pcr_global_params* g, double* T_init, int host_threads);

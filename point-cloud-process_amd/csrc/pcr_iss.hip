@@ -80,6 +80,7 @@ struct iss_cand_before {
 };
 
 // eigenvalues of a symmetric 3x3 matrix (cyclic Jacobi), descending
+// (kept apart from pcr::sym3_jacobi: 32 sweeps, a 1e-17 threshold and no eigenvectors -- the shared form would change this kernel's results)
 __device__ static inline void sym3_eigenvalues(double a00, double a01, double a02, double a11, double a12, double a22, double ev[3]) {
     double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
     for (int sweep = 0; sweep < 32; ++sweep) {

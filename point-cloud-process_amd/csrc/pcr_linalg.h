@@ -147,6 +147,29 @@ __host__ __device__ inline void svd3(const double H[9], double U[9], double s[3]
     else if (nbad >= 2) svd3_complete_two(U, ok[2] ? 2 : (ok[1] ? 1 : 0), ok[2] || ok[1] || ok[0]);
 }
 
+// Cyclic Jacobi of a symmetric 3x3: A ends diagonal (the eigenvalues), the columns of Q (identity on entry) are its eigenvectors.  Not contracted.
+__host__ __device__ inline void sym3_jacobi(double A[3][3], double Q[3][3]) {
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]), diag = fabs(A[0][0]) + fabs(A[1][1]) + fabs(A[2][2]);
+        if (off <= 1e-300 || off <= 1e-18 * diag) break;
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = A[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+            const double arp = A[r][p], arq = A[r][q];
+            A[p][p] -= t * apq; A[q][q] += t * apq;
+            A[p][q] = A[q][p] = 0.0;
+            A[r][p] = A[p][r] = c * arp - s * arq; A[r][q] = A[q][r] = s * arp + c * arq;
+#pragma unroll   // (both loops: A and Q stay in registers, no scratch memory in the kernels that call this)
+            for (int i = 0; i < 3; ++i) { const double qp = Q[i][p], qq = Q[i][q]; Q[i][p] = c * qp - s * qq; Q[i][q] = s * qp + c * qq; }
+        }
+    }
+}
+
 __host__ __device__ inline void mat3_mul(const double A[9], const double B[9], double C[9]) {
 #pragma clang fp contract(fast)   // see the note at the top of pcr_linalg.h
     for (int i = 0; i < 3; ++i)

@@ -24,6 +24,7 @@
 constexpr int NK_MAX = 16;
 
 // eigen-decomposition of a symmetric 3x3 (cyclic Jacobi): eigenvalues descending, V columns = eigenvectors
+// (the sweep is pcr::sym3_jacobi's, written out: calling it gave normals_kernel another register allocation that measured 2-8 % slower)
 __host__ __device__ static inline void sym3_eig(const double S[6] /* xx xy xz yy yz zz */, double ev[3], double V[9]) {
     double A[3][3] = {{S[0], S[1], S[2]}, {S[1], S[3], S[4]}, {S[2], S[4], S[5]}};
     double Q[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
