@@ -155,6 +155,63 @@ PCR_API void pcr_icp_default_params(pcr_icp_params* p);
 PCR_API int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* target_index, const pcr_icp_params* params,
                     const double T0[16], pcr_icp_result* result);
 
+/* ------------------------------------------------- point-to-plane refinement
+ * refine_registration (Registration/main.py:87-95): o3d registration_icp(source, target, distance_threshold,
+ * result_ransac.transformation, TransformationEstimationPointToPlane()).  Open3D is absent and unpinned in the reference;
+ * this follows its published algorithm ("parity unpinned"):
+ *   Evaluate(T): exact nearest target q (row j) of every s = T p; a correspondence iff |s - q|^2 < max_dist^2 (strict, on
+ *     the squared distance: pcr_nn1's gate); fitness = K / n_source, inlier_rmse = sqrt(sum d^2 / K), both 0 when K = 0.
+ *   Update: r = (s - q) . n_j, J = [s x n_j, n_j] about the world origin, A = sum J J^T, b = sum J r, A x = -b,
+ *     x = (alpha, beta, gamma, tx, ty, tz), U = [Rz(gamma) Ry(beta) Rx(alpha) | t], T <- U T.
+ *   Loop: res = Evaluate(T0); for it = 1 .. max_iter: T <- Update(res) T; prev = res; res = Evaluate(T); stop when
+ *     |prev.fitness - res.fitness| < rel_fitness and |prev.inlier_rmse - res.inlier_rmse| < rel_rmse.
+ * Deviations: with K < 6, or A not positive definite to working precision (an LDL^T pivot d_k <= 1e-12 A_kk or not
+ * finite), the update is the identity, the loop stops and the soft status is PCR_E_TOO_FEW_ASSOC (the result stays valid;
+ * Open3D tests |det A| < 1e-6 instead).  The caller's source cloud is never modified (Open3D works on a copy): every pass
+ * applies the composed T to the original records.                                                                        */
+/* Target normals (n x 3, by target row) for the point-to-plane estimation of main.py:87-95: uploaded once, kept with the
+ * index, released by pcr_index_free; a second call replaces them.  Non-finite entries -> PCR_E_INVALID; zero-length
+ * normals are accepted (Open3D does not check them either).                                                               */
+PCR_API int pcr_index_set_normals(pcr_ctx* ctx, pcr_index* index, const double* normals);
+PCR_API int pcr_index_has_normals(const pcr_index* index); /* main.py:87-95 needs them: 1 / 0 */
+
+typedef struct pcr_icp_plane_params {
+    int32_t max_iter;     /* ICPConvergenceCriteria.max_iteration (main.py:87-95 uses Open3D's default) -> 30 */
+    int32_t reserved;
+    double max_dist;      /* max_correspondence_distance (main.py:89: voxel_size * 0.4); <= 0 or +inf: no gate */
+    double rel_fitness;   /* -> 1e-6 */
+    double rel_rmse;      /* -> 1e-6 */
+} pcr_icp_plane_params;
+
+typedef struct pcr_icp_plane_result {
+    double T[16];          /* row-major 4x4: the composed transformation (RegistrationResult.transformation) */
+    double fitness;        /* of the last evaluation */
+    double inlier_rmse;
+    int64_t n_corr;        /* correspondences of the last evaluation */
+    int32_t iters;         /* updates performed */
+    int32_t status;        /* PCR_OK or PCR_E_TOO_FEW_ASSOC */
+    double fitness_log[PCR_ICP_MAX_LOG + 1]; /* entry 0 = evaluation of T0, entry i = evaluation after update i */
+    double rmse_log[PCR_ICP_MAX_LOG + 1];
+    double device_ms;      /* HIP events around the whole loop */
+    int32_t nn_launches;   /* correspondence searches = evaluations */
+    int32_t reserved;
+} pcr_icp_plane_result;
+
+/* Open3D's ICPConvergenceCriteria defaults as used by main.py:87-95: 30 / 1e-6 / 1e-6; max_dist = 0 (no gate) */
+PCR_API void pcr_icp_plane_default_params(pcr_icp_plane_params* p);
+/* registration_icp(..., TransformationEstimationPointToPlane()) of main.py:87-95 on device-resident inputs.  `index` must
+ * carry normals (PCR_E_INVALID otherwise); max_iter > PCR_ICP_MAX_LOG -> PCR_E_TOO_MANY_ITERS; empty source -> PCR_E_EMPTY.
+ * Returns result->status.                                                                                                */
+PCR_API int pcr_icp_point2plane(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const pcr_icp_plane_params* params,
+                                const double T0[16], pcr_icp_plane_result* result);
+/* One association + accumulation pass of main.py:87-95's estimation without a solve (counterpart of pcr_icp_moments, for
+ * tests): out[0..20] = upper triangle of A row-major, out[21..26] = b, out[27] = K, out[28] = sum d^2.  T may be NULL.   */
+PCR_API int pcr_point2plane_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const double* T, double max_dist,
+                                    double out[29]);
+/* The update of main.py:87-95's estimation on the host (counterpart of pcr_procrustes): solves A x = -b by LDL^T with the
+ * routine the kernel runs and builds U (row-major 4x4).  PCR_E_TOO_FEW_ASSOC when A is not positive definite (x, U = identity). */
+PCR_API int pcr_point2plane_solve(const double A_upper[21], const double b[6], double x[6], double U[16]);
+
 /* Batched scan-pair registration: the loop Registration/main.py:190-216 (read pair, register, keep the pose) for many
  * independent pairs at once.  pairs[i] are caller-owned host buffers (records of `stride` values, x,y,z first: stride 6 is
  * the registration_dataset .bin record of main.py:10-17, stride 4 the KITTI record); T0 may be NULL (identity).

@@ -10,9 +10,11 @@ top-level alias module ``pcp_amd``.
 """
 from . import _lib  # noqa: F401
 from . import synthetic  # noqa: F401
-from .device import Context, DeviceCloud, TargetIndex, default_context, icp_device  # noqa: F401
+from .device import Context, DeviceCloud, TargetIndex, default_context, icp_device, icp_point2plane_device  # noqa: F401
 from .registration import (  # noqa: F401
     ICP,
+    ICPConvergenceCriteria,
+    TransformationEstimationPointToPlane,
     coarse_to_fine_icp,
     KDTreeFlann,
     PointCloud,
@@ -24,6 +26,8 @@ from .registration import (  # noqa: F401
     read_bin_velodyne,
     read_oxford_bin,
     read_velodyne_bin,
+    refine_registration,
+    registration_icp,
     rotmat2quaternion,
     write_reg_result,
 )

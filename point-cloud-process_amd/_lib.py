@@ -123,6 +123,32 @@ class IcpResult(C.Structure):
     ]
 
 
+class IcpPlaneParams(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int32),
+        ("reserved", C.c_int32),
+        ("max_dist", C.c_double),
+        ("rel_fitness", C.c_double),
+        ("rel_rmse", C.c_double),
+    ]
+
+
+class IcpPlaneResult(C.Structure):
+    _fields_ = [
+        ("T", C.c_double * 16),
+        ("fitness", C.c_double),
+        ("inlier_rmse", C.c_double),
+        ("n_corr", C.c_int64),
+        ("iters", C.c_int32),
+        ("status", C.c_int32),
+        ("fitness_log", C.c_double * (PCR_ICP_MAX_LOG + 1)),
+        ("rmse_log", C.c_double * (PCR_ICP_MAX_LOG + 1)),
+        ("device_ms", C.c_double),
+        ("nn_launches", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -156,6 +182,12 @@ SIGNATURES = {
     "pcr_radius_small": (C.c_int, [_vp, _vp, _dp, C.c_int, C.c_double, C.c_int64, _lp, _ip, _dp]),
     "pcr_icp_default_params": (None, [C.POINTER(IcpParams)]),
     "pcr_icp": (C.c_int, [_vp, _vp, _vp, C.POINTER(IcpParams), _dp, C.POINTER(IcpResult)]),
+    "pcr_index_set_normals": (C.c_int, [_vp, _vp, _dp]),
+    "pcr_index_has_normals": (C.c_int, [_vp]),
+    "pcr_icp_plane_default_params": (None, [C.POINTER(IcpPlaneParams)]),
+    "pcr_icp_point2plane": (C.c_int, [_vp, _vp, _vp, C.POINTER(IcpPlaneParams), _dp, C.POINTER(IcpPlaneResult)]),
+    "pcr_point2plane_moments": (C.c_int, [_vp, _vp, _vp, _dp, C.c_double, _dp]),
+    "pcr_point2plane_solve": (C.c_int, [_dp, _dp, _dp, _dp]),
     "pcr_icp_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(Pair), C.c_int64, C.POINTER(IcpParams), C.POINTER(IcpResult), _ip]),
     "pcr_global_default_params": (C.c_int, [C.c_double, C.POINTER(GlobalParams)]),
     "pcr_register_pairs": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(CloudRef), C.c_int64, C.POINTER(PairRef), C.c_int64, C.POINTER(GlobalParams),

@@ -188,6 +188,22 @@ __device__ static inline unsigned int wave_excl_scan_u32(unsigned int v, int lan
     *total = __builtin_amdgcn_readlane((int)inc, 63);
     return inc - v;
 }
+// binary64 wave total in lane 63 (inclusive-scan pattern; lanes without a source add +0.0)
+template <int CTRL, int ROW_MASK>
+__device__ static inline double dpp_add_f64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
+    return v + __hiloint2double(hi, lo);
+}
+__device__ static inline double wave_total_f64(double v) {
+    v = dpp_add_f64<0x111, 0xf>(v);
+    v = dpp_add_f64<0x112, 0xf>(v);
+    v = dpp_add_f64<0x114, 0xf>(v);
+    v = dpp_add_f64<0x118, 0xf>(v);
+    v = dpp_add_f64<0x142, 0xa>(v);
+    v = dpp_add_f64<0x143, 0xc>(v);
+    return v;
+}
 // minimum / maximum over the wave in every lane (lanes without a source keep their own value; lane 63 ends with the result)
 __device__ static inline int wave_min_i32(int v) {
     v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x111, 0xf, 0xf, false));

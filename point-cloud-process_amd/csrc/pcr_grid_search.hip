@@ -117,22 +117,6 @@ __device__ static inline unsigned int wave_incl_scan_max(unsigned int v) {
     v = max(v, dpp_u32<0x143, 0xc>(0u, v));
     return v;
 }
-// binary64 wave total in lane 63 (inclusive-scan pattern; lanes without a source add +0.0)
-template <int CTRL, int ROW_MASK>
-__device__ static inline double dpp_add_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return v + __hiloint2double(hi, lo);
-}
-__device__ static inline double wave_total_f64(double v) {
-    v = dpp_add_f64<0x111, 0xf>(v);
-    v = dpp_add_f64<0x112, 0xf>(v);
-    v = dpp_add_f64<0x114, 0xf>(v);
-    v = dpp_add_f64<0x118, 0xf>(v);
-    v = dpp_add_f64<0x142, 0xa>(v);
-    v = dpp_add_f64<0x143, 0xc>(v);
-    return v;
-}
 
 // all-reduce inside every row of 16 lanes (half of a tile's queries): quad swaps, half mirror, mirror
 __device__ static inline int row16_min(int v) {

@@ -41,6 +41,7 @@ int pcr_index_build(pcr_ctx* ctx, const pcr_cloud* target, int kind, double cell
 int pcr_index_free(pcr_ctx* ctx, pcr_index* idx) {
     if (!idx) return PCR_OK;
     if (!ctx) return PCR_E_INVALID;
+    pcr_point2plane_free(ctx, idx);
     if (idx->kind == PCR_INDEX_GRID) pcr_grid_free(ctx, idx);
     else pcr_brute_free(ctx, idx);
     delete idx;

@@ -85,6 +85,11 @@ struct pcr_index {
     pcr_pt* plain = nullptr;    // targets in original order, centred copy not needed (exact recheck uses these)
     int64_t n_tiles = 0;
     double brute_rt = 0, brute_bias = 0;  // half diagonal of the target box; offset that keeps the contraction positive
+    // point-to-plane refinement (pcr_point2plane.hip): target normals, 3 doubles per record in the order of `sorted` (GRID) / `plain`
+    // (BRUTE), so that a matched point and its normal are fetched by the same position; GRID: position of every target row in `sorted`
+    // (the searches report rows).  Null until pcr_index_set_normals.
+    double* normals = nullptr;
+    int32_t* row_pos = nullptr;
 };
 
 struct pcr_ctx {
@@ -223,6 +228,9 @@ PCR_HIDDEN int pcr_brute_nn1(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q
 PCR_HIDDEN int pcr_brute_last_fallback(pcr_ctx* ctx, unsigned int* out);
 PCR_HIDDEN int pcr_brute_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq, const pcr_xform* x,
                                   double max_d2, int write_back, double* d_moments);
+
+// point-to-plane (pcr_point2plane.hip)
+PCR_HIDDEN void pcr_point2plane_free(pcr_ctx* ctx, pcr_index* idx);   // the normals of an index
 
 constexpr int PCR_NMOM = 20;  // K, Sa[3], Sb[3], Sba[9], Saa, Sbb, Sd2, pad
 

@@ -209,4 +209,58 @@ __host__ __device__ inline void kabsch_from_moments(const double m[18], const do
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Point-to-plane update (Open3D TransformationEstimationPointToPlane as called by Registration/main.py:87-95): A x = -b for the
+// symmetric 6x6 normal matrix given by its upper triangle (row-major, 21 entries), by LDL^T without pivoting (stable for a positive
+// definite matrix), then U = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5] (row-major 4x4).  Not contracted.  Every loop has constant bounds and is
+// unrolled: L and d stay in registers in the single device lane that runs this (no scratch memory).
+// false: A is not positive definite to working precision -- a pivot d_k <= 1e-12 A_kk (the computed pivot of a singular matrix is
+// rounding noise of relative size K 2^-53 of A_kk for K summed terms, either sign) or not finite; x = 0, U = identity then.
+constexpr int sym6_at(int i, int j) { return i <= j ? 6 * i - i * (i - 1) / 2 + (j - i) : 6 * j - j * (j - 1) / 2 + (i - j); }
+__host__ __device__ inline bool point2plane_solve(const double Au[21], const double b[6], double x[6], double U[16]) {
+    double L[6][6], d[6];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double v[6];
+        double dj = Au[sym6_at(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; ++k) { v[k] = L[j][k] * d[k]; dj -= L[j][k] * v[k]; }
+        ok = ok && dj > 1e-12 * Au[sym6_at(j, j)] && dj < INFINITY;
+        d[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double a = Au[sym6_at(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; ++k) a -= L[i][k] * v[k];
+            L[i][j] = a / dj;
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {   // L y = -b
+        double a = -b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) a -= L[i][k] * y[k];
+        y[i] = a;
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {  // L^T x = D^-1 y
+        double a = y[i] / d[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) a -= L[k][i] * x[k];
+        x[i] = a;
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) ok = ok && x[i] - x[i] == 0.0;   // finite
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = ok ? x[i] : 0.0;
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    U[0] = cb * cg; U[1] = sa * sb * cg - ca * sg; U[2] = ca * sb * cg + sa * sg; U[3] = x[3];
+    U[4] = cb * sg; U[5] = sa * sb * sg + ca * cg; U[6] = ca * sb * sg - sa * cg; U[7] = x[4];
+    U[8] = -sb;     U[9] = sa * cb;                U[10] = ca * cb;               U[11] = x[5];
+    U[12] = U[13] = U[14] = 0.0; U[15] = 1.0;
+    return ok;
+}
+
 }  // namespace pcr

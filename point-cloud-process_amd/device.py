@@ -262,6 +262,36 @@ class TargetIndex:
             own.free()
         return m, o, s.value
 
+    def set_normals(self, normals):
+        """Target normals (N,3) by target row for the point-to-plane refinement (Registration/main.py:87-95); kept with the index."""
+        nrm = L.as_f64(normals)
+        if nrm.shape != (self.n, 3):
+            raise ValueError(f"expected ({self.n}, 3) normals, got shape {nrm.shape}")
+        L.check(L.lib().pcr_index_set_normals(self.ctx.handle, self.handle, L.dptr(nrm)), self.ctx.handle)
+        return self
+
+    @property
+    def has_normals(self):
+        return bool(L.lib().pcr_index_has_normals(self.handle))
+
+    def point2plane_moments(self, source, T=None, max_correspondence_distance=0.0):
+        """One association + accumulation pass of the point-to-plane estimation -> (A (6,6), b (6,), K, sum_d2)."""
+        own = None
+        if not isinstance(source, DeviceCloud):
+            source = own = DeviceCloud.upload(source, self.ctx)
+        out = np.zeros(29)
+        Tc = L.as_f64(np.eye(4) if T is None else T).reshape(16)
+        try:
+            L.check(L.lib().pcr_point2plane_moments(self.ctx.handle, source.handle, self.handle, L.dptr(Tc), float(max_correspondence_distance),
+                                                    L.dptr(out)), self.ctx.handle)
+        finally:
+            if own is not None:
+                own.free()
+        A = np.zeros((6, 6))
+        A[np.triu_indices(6)] = out[:21]
+        A = A + np.triu(A, 1).T
+        return A, out[21:27].copy(), int(round(out[27])), float(out[28])
+
     def free(self):
         if self._h:
             L.lib().pcr_index_free(self.ctx.handle, self._h)
@@ -304,4 +334,33 @@ def icp_device(source: DeviceCloud, index: TargetIndex, T0, *, mode="compat", ma
         "device_ms": res.device_ms,
         "nn_kernel_ms": res.nn_kernel_ms,
         "nn_launches": res.nn_launches,
+    }
+
+
+def icp_point2plane_device(source: DeviceCloud, index: TargetIndex, T0, *, max_correspondence_distance, max_iteration=30,
+                           relative_fitness=1e-6, relative_rmse=1e-6):
+    """pcr_icp_point2plane on device-resident inputs (Registration/main.py:87-95) -> dict with T, fitness, inlier_rmse, n_corr,
+    iters, status, the per-evaluation logs and timings.  The source cloud is not modified."""
+    p = L.IcpPlaneParams()
+    L.lib().pcr_icp_plane_default_params(C.byref(p))
+    p.max_iter = int(max_iteration)
+    p.max_dist = float(max_correspondence_distance)
+    p.rel_fitness = float(relative_fitness)
+    p.rel_rmse = float(relative_rmse)
+    res = L.IcpPlaneResult()
+    T0c = L.as_f64(T0).reshape(16)
+    st = L.lib().pcr_icp_point2plane(index.ctx.handle, source.handle, index.handle, C.byref(p), L.dptr(T0c), C.byref(res))
+    L.check(st, index.ctx.handle)
+    n = res.nn_launches
+    return {
+        "T": np.array(res.T[:]).reshape(4, 4),
+        "fitness": res.fitness,
+        "inlier_rmse": res.inlier_rmse,
+        "n_corr": res.n_corr,
+        "iters": res.iters,
+        "status": res.status,
+        "fitness_log": list(res.fitness_log[:n]),
+        "rmse_log": list(res.rmse_log[:n]),
+        "device_ms": res.device_ms,
+        "nn_launches": n,
     }

@@ -330,7 +330,8 @@ def preprocess_point_cloud(pcd, voxel_size, ctx=None):
 
 def prepare_dataset(path_src, path_trg, voxel_size, ctx=None):
     """main.py:50-65 -> (source, target, source_down, target_down, source_fpfh, target_fpfh).  The full-resolution
-    normals main.py:54,57 computes are only used by its dead point-to-plane refinement and are not computed here."""
+    normals main.py:54,57 computes are only used by its point-to-plane refinement, which nothing calls: they are not computed here
+    (registration.refine_registration estimates them when its target has none)."""
     source = PointCloud(read_bin_velodyne(path_src))
     target = PointCloud(read_bin_velodyne(path_trg))
     source_down, source_fpfh = preprocess_point_cloud(source, voxel_size, ctx=ctx)

@@ -14,12 +14,13 @@ from collections import defaultdict
 import numpy as np
 
 from . import _lib as L
-from .device import Context, DeviceCloud, TargetIndex, default_context, icp_device, points_of
+from .device import Context, DeviceCloud, TargetIndex, default_context, icp_device, icp_point2plane_device, points_of
 
 __all__ = [
     "PointCloud",
     "KDTreeFlann",
     "icp_point2point",
+    "ICPConvergenceCriteria", "TransformationEstimationPointToPlane", "registration_icp", "refine_registration",
     "ICP", "coarse_to_fine_icp",
     "find_associations",
     "procrustes_transformation",
@@ -183,6 +184,87 @@ def ICP(src_cloud, tgt_cloud, *, init=None, max_iteration=50, R_diff_thres=1e-5,
     log["n_assoc"] = [res["n_assoc"]]
     log["cost"] = [res["cost"]]
     return res["T"], log
+
+
+class ICPConvergenceCriteria:
+    """o3d.pipelines.registration.ICPConvergenceCriteria with Open3D's defaults (what main.py:92-94 gets by passing none)."""
+
+    def __init__(self, relative_fitness=1e-6, relative_rmse=1e-6, max_iteration=30):
+        self.relative_fitness = float(relative_fitness)
+        self.relative_rmse = float(relative_rmse)
+        self.max_iteration = int(max_iteration)
+
+    def __repr__(self):
+        return (f"ICPConvergenceCriteria(relative_fitness={self.relative_fitness:e}, relative_rmse={self.relative_rmse:e}, "
+                f"max_iteration={self.max_iteration})")
+
+
+class TransformationEstimationPointToPlane:
+    """o3d.pipelines.registration.TransformationEstimationPointToPlane (main.py:94): names the estimation method of registration_icp."""
+
+    def __repr__(self):
+        return "TransformationEstimationPointToPlane"
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, estimation_method=None, criteria=None, *, nn="grid", ctx=None):
+    """o3d.pipelines.registration.registration_icp as called at main.py:92-94: point-to-plane ICP from ``init`` (default identity)
+    -> RegistrationResult (transformation, fitness, inlier_rmse; ``info`` holds iterations, status and the per-evaluation logs).
+
+    ``target`` is a cloud-like object with ``.normals`` (N,3), or a TargetIndex that already carries normals
+    (TargetIndex.set_normals).  Like Open3D, a target without normals raises RuntimeError and ``source`` is left untouched.
+    Only TransformationEstimationPointToPlane (the default) is implemented here; point-to-point ICP is icp_point2point / ICP."""
+    from .global_registration import RegistrationResult
+
+    estimation_method = TransformationEstimationPointToPlane() if estimation_method is None else estimation_method
+    if not isinstance(estimation_method, TransformationEstimationPointToPlane):
+        name = estimation_method.__name__ if isinstance(estimation_method, type) else type(estimation_method).__name__
+        raise NotImplementedError(f"registration_icp: estimation method {name} is not implemented (TransformationEstimationPointToPlane is)")
+    criteria = ICPConvergenceCriteria() if criteria is None else criteria
+    T0 = np.eye(4) if init is None else np.array(init, dtype=np.float64).reshape(4, 4)
+    no_normals = ("TransformationEstimationPointToPlane and TransformationEstimationColoredICP require pre-computed normal vectors "
+                  "for target PointCloud.")
+    if isinstance(target, TargetIndex):
+        if not target.has_normals:
+            raise RuntimeError(no_normals)
+        index, own = target, False
+        ctx = target.ctx
+    else:
+        normals = getattr(target, "normals", None)
+        if normals is None or len(normals) == 0:
+            raise RuntimeError(no_normals)
+        ctx = ctx or default_context()
+        index, own = TargetIndex(points_of(target), kind=nn, ctx=ctx), True
+    src_dev = None
+    try:
+        if own:
+            index.set_normals(np.asarray(normals, dtype=np.float64)[:, :3])
+        src_dev = DeviceCloud.upload(points_of(source), ctx)
+        res = icp_point2plane_device(src_dev, index, T0, max_correspondence_distance=max_correspondence_distance,
+                                     max_iteration=criteria.max_iteration, relative_fitness=criteria.relative_fitness,
+                                     relative_rmse=criteria.relative_rmse)
+    finally:
+        if src_dev is not None:
+            src_dev.free()
+        if own:
+            index.free()
+    return RegistrationResult(res["T"], res["fitness"], res["inlier_rmse"], info=res)
+
+
+def refine_registration(source, target, source_fpfh, target_fpfh, voxel_size, result_ransac, *, nn="grid", ctx=None):
+    """main.py:87-95: point-to-plane ICP on the original clouds from the global registration's transform, with the strict
+    threshold voxel_size * 0.4.  ``result_ransac`` is an explicit argument (the reference reads an undefined global);
+    the descriptors are unused, as in the reference.  A target without ``.normals`` gets them from
+    estimate_normals_hybrid(radius=2 * voxel_size, max_nn=30), what main.py:54,57 computes for this stage (one host round trip)."""
+    distance_threshold = voxel_size * 0.4
+    init = getattr(result_ransac, "transformation", result_ransac)
+    if not isinstance(target, TargetIndex) and getattr(target, "normals", None) is None:
+        from .global_registration import estimate_normals_hybrid
+
+        pts = np.ascontiguousarray(points_of(target)[:, :3], dtype=np.float64)
+        with_normals = PointCloud(pts)
+        with_normals.normals = estimate_normals_hybrid(pts, radius=2.0 * voxel_size, max_nn=30, ctx=ctx)
+        target = with_normals
+    return registration_icp(source, target, distance_threshold, init, TransformationEstimationPointToPlane(), nn=nn, ctx=ctx)
 
 
 def find_associations(src_points, tgt_tree=None, dist_thres=5.0):
