@@ -392,6 +392,45 @@ PCR_API int pcr_register_pairs(pcr_ctx* const* ctxs, int n_ctx, const pcr_cloud_
  * the point itself included (scipy query_ball_point).                        */
 PCR_API int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts, int32_t* labels_out, int32_t* n_clusters_out);
 
+/* ------------------------------------------------------ ground segmentation
+ * ground_segmentation (Cluster_dbscan/clustering.py:36-95), the step in front of DBSCAN in its main() (clustering.py:158-160):
+ * RANSAC plane fit, the inliers of the best plane removed.  Trial j takes the rows samples[3j .. 3j+2] (the caller draws them:
+ * clustering.py:57 uses np.random, and the library has no generator for this step), p0,p1,p2 = their points,
+ *   c = cross(p0 - p1, p0 - p2), nrm = c / sqrt((cx*cx + cy*cy) + cz*cz)       (a degenerate triple: 0/0 = NaN, like the reference)
+ *   row i is an inlier iff |((vx*nx + vy*ny) + vz*nz)| < tau, v = point_i - p0   (strict; false for NaN)
+ * in binary64 on the stored coordinates, this operation order, no contraction: a NumPy float64 restatement agrees on every point.
+ * (The reference evaluates in float32 because its reader returns float32: labels can differ only within a rounding band of tau.)
+ * The running best is replaced on a strictly larger count (the earlier of two equal trials wins), and right after a replacement
+ * the loop breaks when best / n > ratio (clustering.py:75-81).  Every hypothesis is scored whatever the break: counts_out holds
+ * all n_hyp true counts, `evaluated` says how many trials the reference would have run.
+ * Outputs, each optional: the outlier rows of the winner in ascending row order as a new device-resident cloud (ids 0..m-1, no
+ * bounding box, not reordered; m may be 0) and as a row list (first n_outliers entries), the inlier flag of every row.
+ * Every trial degenerate (clustering.py:83 indexes with None): PCR_E_TOO_FEW_ASSOC, no cloud, best_hyp = -1, counts_out valid.
+ * PCR_E_INVALID: tau not finite, n_hyp < 1, a sample row outside [0, n), NULL samples / params / result.  Empty cloud: PCR_E_EMPTY. */
+typedef struct pcr_ground_params {
+    double tau;           /* clustering.py:17 -> 0.6 */
+    double ratio;         /* clustering.py:19 -> 0.5 */
+    int32_t n_hyp;        /* clustering.py:18 -> 35  */
+    int32_t reserved_i;
+    double reserved[4];
+} pcr_ground_params;
+typedef struct pcr_ground_result {
+    int32_t best_hyp, evaluated;  /* winning trial; trials the reference would have run (break trial + 1, or n_hyp) */
+    int64_t n_inliers, n_outliers;
+    double point[3], normal[3];   /* p0 and unit normal of the winner */
+    double reserved[4];
+} pcr_ground_result;
+PCR_API void pcr_ground_default_params(pcr_ground_params* p);   /* 0.6, 0.5, 35 */
+/* The running-best / early-break rule of clustering.py:75-81 over the counts of all trials, on the host -- the source the device's
+ * finishing step compiles (counterpart of pcr_point2plane_solve).  The break test is (double)best / (double)n > ratio.
+ * PCR_E_TOO_FEW_ASSOC when no count is positive (best_hyp = -1, evaluated = n_hyp); PCR_E_INVALID: NULL pointer, n_hyp < 1,
+ * n < 1, a count outside [0, n].                                                                                              */
+PCR_API int pcr_ground_select(const int64_t* counts, int32_t n_hyp, int64_t n, double ratio, int32_t* best_hyp, int32_t* evaluated);
+PCR_API int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* samples /* n_hyp x 3 caller rows */,
+                                    const pcr_ground_params* params, pcr_cloud** outliers_out /* NULL = not wanted */,
+                                    int32_t* outlier_rows_out /* n or NULL */, uint8_t* inlier_mask_out /* n or NULL */,
+                                    int64_t* counts_out /* n_hyp or NULL: every hypothesis's true count */, pcr_ground_result* result);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

@@ -149,6 +149,28 @@ class IcpPlaneResult(C.Structure):
     ]
 
 
+class GroundParams(C.Structure):
+    _fields_ = [
+        ("tau", C.c_double),
+        ("ratio", C.c_double),
+        ("n_hyp", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("reserved", C.c_double * 4),
+    ]
+
+
+class GroundResult(C.Structure):
+    _fields_ = [
+        ("best_hyp", C.c_int32),
+        ("evaluated", C.c_int32),
+        ("n_inliers", C.c_int64),
+        ("n_outliers", C.c_int64),
+        ("point", C.c_double * 3),
+        ("normal", C.c_double * 3),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -213,6 +235,9 @@ SIGNATURES = {
     "pcr_prep_free": (C.c_int, [_vp, _vp]),
     "pcr_global_registration": (C.c_int, [_vp, _vp, _vp, C.POINTER(RansacParams), C.c_int, C.POINTER(RansacResult)]),
     "pcr_dbscan": (C.c_int, [_vp, _vp, C.c_double, C.c_int, _ip, _ip]),
+    "pcr_ground_default_params": (None, [C.POINTER(GroundParams)]),
+    "pcr_ground_select": (C.c_int, [_lp, C.c_int32, C.c_int64, C.c_double, _ip, _ip]),
+    "pcr_ground_segmentation": (C.c_int, [_vp, _vp, _lp, C.POINTER(GroundParams), C.POINTER(_vp), _ip, C.POINTER(C.c_uint8), _lp, C.POINTER(GroundResult)]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_read": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
