@@ -39,7 +39,8 @@ enum {
     PCR_E_HIP = -4,         /* HIP runtime error; see pcr_last_error()        */
     PCR_E_NO_DEVICE = -5,
     PCR_E_UNSUPPORTED = -6,
-    PCR_E_TOO_MANY_ITERS = -7
+    PCR_E_TOO_MANY_ITERS = -7,
+    PCR_E_SINGULAR = -8     /* mixture component without points or with a covariance that is not positive definite */
 };
 
 typedef struct pcr_ctx pcr_ctx;
@@ -430,6 +431,63 @@ PCR_API int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const 
                                     const pcr_ground_params* params, pcr_cloud** outliers_out /* NULL = not wanted */,
                                     int32_t* outlier_rows_out /* n or NULL */, uint8_t* inlier_mask_out /* n or NULL */,
                                     int64_t* counts_out /* n_hyp or NULL: every hypothesis's true count */, pcr_ground_result* result);
+
+/* ------------------------------------------------------------- Gaussian mixture
+ * class GMM (Cluster_KMeans_GMM/GMM.py:13-71): EM with full covariances on a device-resident cloud.
+ *   init (GMM.py:25-27): the caller's means0 (the reference draws np.random.random((k, dim))), covariances I, weights 1/k, last_nll = inf
+ *   E (GMM.py:31-35):  gamma[k,n] ~ w_k N(x_n; mu_k, Sigma_k), normalised over k
+ *   M (GMM.py:38-53):  N_k = sum gamma; mu_k = sum gamma x / N_k; Sigma_k = sum gamma (x - mu_k)(x - mu_k)^T / N_k about the NEW means
+ *                      with the SAME gamma, no regularisation; w_k = N_k / n
+ *   stop (GMM.py:56-63): nll = -sum_n log sum_k w_k N(x_n; .) of the NEW parameters; last_nll - nll < tol: break (the updated
+ *                      parameters stay); else last_nll = nll
+ *   predict (GMM.py:65-70): argmax_k w_k N(x; mu_k, Sigma_k), the lowest k on ties.
+ * Deviation 1, the log domain: Sigma_k = L L^T, a_k(x) = log w_k - dim/2 log 2pi - sum_i log L_ii - |L^-1 (x - mu_k)|^2 / 2,
+ *   m = max_k a_k, gamma_k = exp(a_k - m) / sum_j exp(a_j - m), log-likelihood of the point = m + log sum_j exp(a_j - m).  Equal to
+ *   the reference to rounding wherever its densities do not underflow, and defined where it gives 0/0 (any point more than ~38
+ *   units from every mean of an identity-covariance start).
+ * Deviation 2, failure: a component whose N_k is 0 or not finite, or whose covariance has a Cholesky pivot that is not positive or
+ *   not finite, ends pcr_gmm_fit with PCR_E_SINGULAR; result->bad_iter / bad_component name the iteration (1-based) and the
+ *   component (scipy raises LinAlgError / ValueError at that point); the outputs are not written.
+ * Limits: 1 <= k <= PCR_GMM_MAX_K, dim 2 or 3 (dim 2 uses x and y of the records and ignores z), max_iter >= 1: otherwise
+ *   PCR_E_INVALID; an empty cloud: PCR_E_EMPTY.  means (k,dim), covs (k,dim,dim), weights (k) row-major; of a covariance the lower
+ *   triangle is read.  Sums are taken in a fixed order without floating-point atomics: two calls give the same bits.           */
+#define PCR_GMM_MAX_K 32
+typedef struct pcr_gmm_params {
+    int32_t n_clusters;   /* GMM.py:14 */
+    int32_t dim;          /* data.shape[1]: 2 or 3 -> 3 */
+    int32_t max_iter;     /* GMM.py:14 -> 50 */
+    int32_t reserved_i;
+    double tol;           /* GMM.py:14 -> 0.001 */
+    double reserved[4];
+} pcr_gmm_params;
+typedef struct pcr_gmm_result {
+    int32_t iters;          /* EM iterations performed (trips of the loop GMM.py:29) */
+    int32_t converged;      /* the loop broke on the rule of GMM.py:61 */
+    int32_t bad_component;  /* PCR_E_SINGULAR: the (lowest) failing component, -1 otherwise */
+    int32_t bad_iter;       /* PCR_E_SINGULAR: the iteration it failed in, 1-based */
+    double nll;             /* negative log-likelihood of the returned parameters */
+    double device_ms;       /* HIP events around the whole loop */
+    int32_t passes;         /* streaming passes over the cloud the loop needs: 2 iters + 1 */
+    int32_t reserved_i;
+    double reserved[4];
+} pcr_gmm_result;
+PCR_API void pcr_gmm_default_params(pcr_gmm_params* p);   /* 1 cluster, dim 3, 50, 0.001 */
+/* GMM.fit (GMM.py:23-63), the whole loop with its state on the device.  nll_hist_out (max_iter entries or NULL): nll after every
+ * iteration, the first result->iters entries are written.                                                                     */
+PCR_API int pcr_gmm_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_gmm_params* params, const double* means0 /* k*dim */, double* means_out,
+                        double* covs_out /* k*dim*dim */, double* weights_out /* k */, double* nll_hist_out, pcr_gmm_result* result);
+/* Exactly one E + M step (GMM.py:31-53) from the given parameters, for callers with their own loop and for tests: the new
+ * parameters, N_k, and *loglik_in_out = the log-likelihood of the INPUT parameters.  The status comes from the input parameters
+ * only (PCR_E_SINGULAR: an input covariance is not positive definite); what an empty component gives (0/0) is returned as it is.
+ * Every output may be NULL.                                                                                                   */
+PCR_API int pcr_gmm_step(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const double* means, const double* covs, const double* weights,
+                         double* means_out, double* covs_out, double* weights_out, double* nk_out, double* loglik_in_out);
+/* GMM.predict (GMM.py:65-70): labels_out[n] by caller row; resp_out (n,k) or NULL: the responsibilities gamma; loglik_out or NULL. */
+PCR_API int pcr_gmm_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const double* means, const double* covs, const double* weights,
+                            int32_t* labels_out, double* resp_out, double* loglik_out);
+/* a_k(x) of deviation 1 for one point and one component on the host -- the source the kernels compile (counterpart of
+ * pcr_ground_select).  PCR_E_SINGULAR: cov is not positive definite; PCR_E_INVALID: dim not 2 or 3, weight not in (0, inf).      */
+PCR_API int pcr_gmm_log_density(int dim, const double* x, const double* mean, const double* cov, double weight, double* a_out);
 
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */

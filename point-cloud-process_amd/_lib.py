@@ -24,6 +24,7 @@ PCR_E_HIP = -4
 PCR_E_NO_DEVICE = -5
 PCR_E_UNSUPPORTED = -6
 PCR_E_TOO_MANY_ITERS = -7
+PCR_E_SINGULAR = -8
 
 PCR_INDEX_GRID = 0
 PCR_INDEX_BRUTE = 1
@@ -32,6 +33,7 @@ PCR_ICP_TOTAL = 1
 PCR_RMETRIC_FROBENIUS = 0
 PCR_RMETRIC_GEODESIC = 1
 PCR_ICP_MAX_LOG = 256
+PCR_GMM_MAX_K = 32
 
 
 class IcpParams(C.Structure):
@@ -171,6 +173,31 @@ class GroundResult(C.Structure):
     ]
 
 
+class GmmParams(C.Structure):
+    _fields_ = [
+        ("n_clusters", C.c_int32),
+        ("dim", C.c_int32),
+        ("max_iter", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("tol", C.c_double),
+        ("reserved", C.c_double * 4),
+    ]
+
+
+class GmmResult(C.Structure):
+    _fields_ = [
+        ("iters", C.c_int32),
+        ("converged", C.c_int32),
+        ("bad_component", C.c_int32),
+        ("bad_iter", C.c_int32),
+        ("nll", C.c_double),
+        ("device_ms", C.c_double),
+        ("passes", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -238,6 +265,11 @@ SIGNATURES = {
     "pcr_ground_default_params": (None, [C.POINTER(GroundParams)]),
     "pcr_ground_select": (C.c_int, [_lp, C.c_int32, C.c_int64, C.c_double, _ip, _ip]),
     "pcr_ground_segmentation": (C.c_int, [_vp, _vp, _lp, C.POINTER(GroundParams), C.POINTER(_vp), _ip, C.POINTER(C.c_uint8), _lp, C.POINTER(GroundResult)]),
+    "pcr_gmm_default_params": (None, [C.POINTER(GmmParams)]),
+    "pcr_gmm_fit": (C.c_int, [_vp, _vp, C.POINTER(GmmParams), _dp, _dp, _dp, _dp, _dp, C.POINTER(GmmResult)]),
+    "pcr_gmm_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "pcr_gmm_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "pcr_gmm_log_density": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_read": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),

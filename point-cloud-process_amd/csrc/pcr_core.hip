@@ -24,6 +24,7 @@ const char* pcr_strerror(int s) {
         case PCR_E_NO_DEVICE: return "no HIP device (libpcr.so needs an AMD GPU; there is no CPU fallback)";
         case PCR_E_UNSUPPORTED: return "unsupported";
         case PCR_E_TOO_MANY_ITERS: return "max_iter exceeds PCR_ICP_MAX_LOG";
+        case PCR_E_SINGULAR: return "singular mixture component (no points, or a covariance that is not positive definite)";
         default: return "unknown status";
     }
 }
