@@ -489,6 +489,67 @@ PCR_API int pcr_gmm_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim
  * pcr_ground_select).  PCR_E_SINGULAR: cov is not positive definite; PCR_E_INVALID: dim not 2 or 3, weight not in (0, inf).      */
 PCR_API int pcr_gmm_log_density(int dim, const double* x, const double* mean, const double* cov, double weight, double* a_out);
 
+/* --------------------------------------------------------------------- K-Means
+ * class K_Means (Cluster_KMeans_GMM/compare_cluster.py:16,105: K_Means(n_clusters=...); fit(X) at :164, labels_ / predict(X) at
+ * :167-170; its KMeans.py is not part of the reference tree): Lloyd's iteration on a device-resident cloud.  x_n are the cloud's
+ * points (x, y, z; dim 2 uses x and y of the records and ignores z), c[k] the centres, c^0 the caller's centers0.
+ *   iteration t = 1..max_iter:
+ *   assign: d2(n,k) = (x-cx)^2 + (y-cy)^2 (+ (z-cz)^2) in binary64, in this direct form (never |x|^2 + |c|^2 - 2 x.c), under
+ *           c^{t-1}; label_n = argmin_k d2, the lowest k on ties like np.argmin (compared with <)
+ *   sums:   N_k = integer count of the points with label k (exact); S_k = sum of those points; J^{t-1} = sum_n min_k d2(n,k), the
+ *           inertia of c^{t-1}
+ *   update: c^t[k] = S_k / N_k where N_k > 0; an empty cluster keeps c^{t-1}[k]: it is not relocated, does not become NaN and is
+ *           not an error
+ *   stop:   shift_t = max_k |c^t[k] - c^{t-1}[k]|_2; shift_t <= tol ends the loop with converged = 1, otherwise it ends at
+ *           t = max_iter with converged = 0.  tol = 0 is legal and means "until the assignment repeats": equal labels give
+ *           bit-identical sums, hence shift = 0 exactly.
+ *   After the loop one final pass under the final centres gives the labels (by caller row), the final counts and
+ *   inertia = sum min d2: the numbers pcr_kmeans_fit reports (scikit-learn's labels_ and inertia_).
+ *   Histories (max_iter entries each, the first result->iters are written): inertia_hist[t-1] = J^{t-1}, shift_hist[t-1] = shift_t.
+ * Sums are binary64 in a fixed order without floating-point atomics: two calls on the same cloud give the same bits.  A cloud laid
+ * out for a grid index (pcr_cloud_prepare: records in Morton order, id = caller row) gives its labels by caller row; its centres
+ * differ by the summation order only.
+ * Limits: 1 <= k <= PCR_KMEANS_MAX_K (= PCR_GMM_MAX_K: the two models seed each other), dim 2 or 3, max_iter >= 1, tol >= 0 and
+ * finite, every entry of centers0 / centers finite, no NULL handle or required pointer: otherwise PCR_E_INVALID; an empty cloud:
+ * PCR_E_EMPTY.  All argument checks come before anything touches the device.  centres, sums: (k,dim) row-major.             */
+#define PCR_KMEANS_MAX_K 32
+typedef struct pcr_kmeans_params {
+    int32_t n_clusters;   /* compare_cluster.py:105 -> 2 */
+    int32_t dim;          /* 2 or 3 -> 3 */
+    int32_t max_iter;     /* -> 300 */
+    int32_t reserved_i;
+    double tol;           /* on shift_t, absolute -> 1e-4 */
+    double reserved[4];
+} pcr_kmeans_params;
+typedef struct pcr_kmeans_result {
+    int32_t iters;          /* iterations performed */
+    int32_t converged;      /* shift_t <= tol fired */
+    int32_t n_empty;        /* clusters without points under the final centres */
+    int32_t reserved_i;
+    double inertia;         /* sum min d2 under the final centres */
+    double shift;           /* shift_t of the last iteration */
+    double device_ms;       /* HIP events around the loop and the final pass */
+    double reserved[4];
+} pcr_kmeans_result;
+PCR_API void pcr_kmeans_default_params(pcr_kmeans_params* p);   /* 2 clusters, dim 3, 300, 1e-4 */
+/* K_Means.fit: the whole loop with its state on the device, one streaming pass per iteration plus the final one.  labels_out
+ * (int32[n] by caller row), inertia_hist_out, shift_hist_out (max_iter entries each) may be NULL.                             */
+PCR_API int pcr_kmeans_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_kmeans_params* params, const double* centers0 /* k*dim */,
+                           double* centers_out /* k*dim */, int64_t* counts_out /* k */, int32_t* labels_out, double* inertia_hist_out,
+                           double* shift_hist_out, pcr_kmeans_result* result);
+/* Exactly one assign + update from `centers`, for tests and for callers with their own loop: the new centres, N_k, S_k (k*dim;
+ * zeros for an empty cluster), the inertia of the INPUT centres and the shift.  Every output may be NULL.                     */
+PCR_API int pcr_kmeans_step(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const double* centers, double* centers_out, int64_t* counts_out,
+                            double* sums_out, double* inertia_out, double* shift_out);
+/* K_Means.predict: labels_out[n] by caller row under `centers`; counts_out (k) and inertia_out may be NULL. */
+PCR_API int pcr_kmeans_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const double* centers, int32_t* labels_out, int64_t* counts_out,
+                               double* inertia_out);
+/* A small gather by record id: xyz_out[i] = the point the caller uploaded as row rows[i], in the order asked (a row may repeat),
+ * whatever the cloud's layout -- seeding from a resident or prepared cloud does not download it.  m <= 4096; a row outside
+ * [0, n), m < 0 or m > 4096, a NULL pointer: PCR_E_INVALID.  Relies on the record ids being a permutation of [0, n), which every
+ * cloud this library makes satisfies; a row that no record carried would come back as NaN.                                     */
+PCR_API int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows /* m caller rows */, int64_t m, double* xyz_out /* m*3 */);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

@@ -54,6 +54,7 @@ from .global_registration import (  # noqa: F401
 from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from .gmm import GMM  # noqa: F401
+from .kmeans import K_Means  # noqa: F401
 from .batch import register_batch, shard_range  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import evaluate_rt, get_P_diff, is_registration_successful  # noqa: F401

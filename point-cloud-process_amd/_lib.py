@@ -34,6 +34,7 @@ PCR_RMETRIC_FROBENIUS = 0
 PCR_RMETRIC_GEODESIC = 1
 PCR_ICP_MAX_LOG = 256
 PCR_GMM_MAX_K = 32
+PCR_KMEANS_MAX_K = 32
 
 
 class IcpParams(C.Structure):
@@ -198,6 +199,30 @@ class GmmResult(C.Structure):
     ]
 
 
+class KmeansParams(C.Structure):
+    _fields_ = [
+        ("n_clusters", C.c_int32),
+        ("dim", C.c_int32),
+        ("max_iter", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("tol", C.c_double),
+        ("reserved", C.c_double * 4),
+    ]
+
+
+class KmeansResult(C.Structure):
+    _fields_ = [
+        ("iters", C.c_int32),
+        ("converged", C.c_int32),
+        ("n_empty", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("inertia", C.c_double),
+        ("shift", C.c_double),
+        ("device_ms", C.c_double),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -270,6 +295,11 @@ SIGNATURES = {
     "pcr_gmm_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "pcr_gmm_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _dp, _ip, _dp, _dp]),
     "pcr_gmm_log_density": (C.c_int, [C.c_int, _dp, _dp, _dp, C.c_double, _dp]),
+    "pcr_kmeans_default_params": (None, [C.POINTER(KmeansParams)]),
+    "pcr_kmeans_fit": (C.c_int, [_vp, _vp, C.POINTER(KmeansParams), _dp, _dp, _lp, _ip, _dp, _dp, C.POINTER(KmeansResult)]),
+    "pcr_kmeans_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _lp, _dp, _dp, _dp]),
+    "pcr_kmeans_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _ip, _lp, _dp]),
+    "pcr_cloud_download_rows": (C.c_int, [_vp, _vp, _lp, C.c_int64, _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_read": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),

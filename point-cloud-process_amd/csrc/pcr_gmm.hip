@@ -128,44 +128,10 @@ __global__ void __launch_bounds__(64) gmm_init_kernel(gmm_state* __restrict__ st
         if (s_bad[j]) { st->status = PCR_E_SINGULAR; st->stop = 1; st->bad_component = j; st->bad_iter = 0; return; }
 }
 
-// Block total of the per-wave sums in s_part -> this block's slab; the block that arrives last adds the slabs in a fixed order into
-// s_tot and gets true.  The hand-off of point2plane_accumulate_kernel: drained stores -> barrier -> agent-scope release -> ticket;
-// last arriver: agent-scope acquire -> barrier -> plain loads.
+// block_slab_sums (pcr_grid_dev.h) with plain binary64 adds: one slab per block, the last block's fixed-order total in s_tot
 __device__ inline bool gmm_block_sums(const double (*s_part)[GM_NSUM_MAX], int nsum, double* __restrict__ partials, unsigned int* __restrict__ ticket,
                                       double (*s_red)[GM_NSUM_MAX], double* s_tot) {
-    __shared__ unsigned int s_last;
-    __syncthreads();
-    if ((int)threadIdx.x < nsum) {
-        const int t = threadIdx.x;
-        partials[(long long)blockIdx.x * nsum + t] = (s_part[0][t] + s_part[1][t]) + (s_part[2][t] + s_part[3][t]);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (t == gridDim.x - 1) ? 1u : 0u;
-        if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            *ticket = 0;   // ready for the next launch (stream-ordered)
-        }
-    }
-    __syncthreads();
-    if (!s_last) return false;
-    // 8 strided slices of the slabs (slice j: blocks j, j + 8, ... in order), then a fixed tree over the slices
-    for (int idx = threadIdx.x; idx < 8 * nsum; idx += GM_BLOCK) {
-        const int slice = idx / nsum, t = idx - slice * nsum;
-        double v = 0.0;
-        for (long long b = slice; b < (long long)gridDim.x; b += 8) v += partials[b * nsum + t];
-        s_red[slice][t] = v;
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < nsum; t += GM_BLOCK)
-        s_tot[t] = ((s_red[0][t] + s_red[1][t]) + (s_red[2][t] + s_red[3][t])) + ((s_red[4][t] + s_red[5][t]) + (s_red[6][t] + s_red[7][t]));
-    __syncthreads();
-    return true;
+    return block_slab_sums<GM_NSUM_MAX>(s_part, nsum, partials, ticket, s_red, s_tot, [](double x, double y, int) { return x + y; });
 }
 
 // the block's tile: GM_PTS points per lane (zeros behind the end), and the constants in LDS

@@ -259,3 +259,47 @@ __device__ static inline void wave_sync() {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+
+// ---------------------------------------------------------------- block slabs with a last-block ticket (256 threads = four waves)
+// Block total of the per-wave values in s_part -> this block's slab of `nsum` values in `partials`; the block that arrives last adds
+// the slabs in a fixed order into s_tot and gets true.  add(a, b, t) combines two values of slot t (a plain + for a double; an integer
+// slot keeps its bits in the double).  The hand-off of point2plane_accumulate_kernel: drained stores -> barrier -> agent-scope release
+// -> ticket; last arriver: agent-scope acquire -> barrier -> plain loads.  The ticket word is re-armed for the next launch.
+template <int NSUM_MAX, class Add>
+__device__ static inline bool block_slab_sums(const double (*s_part)[NSUM_MAX], int nsum, double* __restrict__ partials, unsigned int* __restrict__ ticket,
+                                              double (*s_red)[NSUM_MAX], double* s_tot, Add add) {
+    __shared__ unsigned int s_last;
+    __syncthreads();
+    if ((int)threadIdx.x < nsum) {
+        const int t = threadIdx.x;
+        partials[(long long)blockIdx.x * nsum + t] = add(add(s_part[0][t], s_part[1][t], t), add(s_part[2][t], s_part[3][t], t), t);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s_last = (t == gridDim.x - 1) ? 1u : 0u;
+        if (s_last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            *ticket = 0;   // ready for the next launch (stream-ordered)
+        }
+    }
+    __syncthreads();
+    if (!s_last) return false;
+    // 8 strided slices of the slabs (slice j: blocks j, j + 8, ... in order), then a fixed tree over the slices
+    for (int idx = threadIdx.x; idx < 8 * nsum; idx += (int)blockDim.x) {
+        const int slice = idx / nsum, t = idx - slice * nsum;
+        double v = 0.0;   // all bits zero: the integer 0 as well
+        for (long long b = slice; b < (long long)gridDim.x; b += 8) v = add(v, partials[b * nsum + t], t);
+        s_red[slice][t] = v;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < nsum; t += (int)blockDim.x)
+        s_tot[t] = add(add(add(s_red[0][t], s_red[1][t], t), add(s_red[2][t], s_red[3][t], t), t),
+                       add(add(s_red[4][t], s_red[5][t], t), add(s_red[6][t], s_red[7][t], t), t), t);
+    __syncthreads();
+    return true;
+}

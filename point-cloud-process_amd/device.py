@@ -141,6 +141,13 @@ class DeviceCloud:
         L.check(L.lib().pcr_cloud_download_f64(self.ctx.handle, self.handle, L.dptr(out)), self.ctx.handle)
         return out
 
+    def download_rows(self, rows):
+        """(m,3) points of the caller rows `rows` (m <= 4096, any order, repeats allowed) without downloading the cloud."""
+        rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        out = np.empty((len(rows), 3), dtype=np.float64)
+        L.check(L.lib().pcr_cloud_download_rows(self.ctx.handle, self.handle, L.lptr(rows), len(rows), L.dptr(out)), self.ctx.handle)
+        return out
+
     def transform(self, T):
         T = L.as_f64(T).reshape(16)
         L.check(L.lib().pcr_cloud_transform(self.ctx.handle, self.handle, L.dptr(T)), self.ctx.handle)

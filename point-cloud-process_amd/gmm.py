@@ -17,10 +17,10 @@ from .device import DeviceCloud, default_context
 __all__ = ["GMM"]
 
 
-def _as_cloud(data, dim, ctx):
-    """-> (DeviceCloud, dim, owned).  Arrays: (n,2) or (n,3); 2-D rows are uploaded as (x, y, 0)."""
+def _as_points(data, dim):
+    """-> (DeviceCloud or (n,3) array, dim), nothing uploaded.  Arrays: (n,2) or (n,3); 2-D rows become (x, y, 0)."""
     if isinstance(data, DeviceCloud):
-        return data, 3 if dim is None else int(dim), False
+        return data, 3 if dim is None else int(dim)
     arr = np.asarray(getattr(data, "points", data))
     if arr.ndim != 2:
         raise ValueError(f"expected an (n,2) or (n,3) point array, got shape {arr.shape}")
@@ -35,7 +35,15 @@ def _as_cloud(data, dim, ctx):
         if arr.dtype != np.float32:
             arr = arr.astype(np.float64)
         arr = np.column_stack([arr, np.zeros(len(arr), dtype=arr.dtype)])
-    return DeviceCloud.upload(arr, ctx or default_context()), dim, True
+    return arr, dim
+
+
+def _as_cloud(data, dim, ctx):
+    """-> (DeviceCloud, dim, owned): a DeviceCloud as it is, anything else uploaded."""
+    pts, dim = _as_points(data, dim)
+    if isinstance(pts, DeviceCloud):
+        return pts, dim, False
+    return DeviceCloud.upload(pts, ctx or default_context()), dim, True
 
 
 class GMM(object):
