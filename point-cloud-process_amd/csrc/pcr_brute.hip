@@ -489,8 +489,6 @@ static void brute_scratch_free(pcr_ctx* ctx, brute_scratch* sc) {
     sc->cand = nullptr; sc->res = nullptr; sc->flag_list = nullptr;
 }
 
-constexpr int BR_FLAG_COUNT_WORD = 120, BR_FLAG_SEEN_WORD = 121;  // words of ctx->d_counters
-
 // sweep -> merge -> exact fallback; leaves the per-query exact result in sc->res (query order)
 static int brute_search(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int64_t nq, const pcr_xform* x, double max_d2, bool gate_bounds,
                         brute_scratch* sc) {
@@ -508,7 +506,7 @@ static int brute_search(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int
     const pcr_xform xx = x ? *x : xi;
     const int has_x = x ? 1 : 0;
     const double ox = idx->view.origin[0], oy = idx->view.origin[1], oz = idx->view.origin[2];
-    unsigned int* flag_count = ctx->d_counters + BR_FLAG_COUNT_WORD;  // zero at context creation, re-armed by brute_final_kernel
+    unsigned int* flag_count = pcr_counter(ctx, PCR_CW_BRUTE_FLAGS);  // zero at context creation, re-armed by brute_final_kernel
     dim3 grid((unsigned)((nq + BR_QPB - 1) / BR_QPB), (unsigned)sc->splits);
     pcr_prof_mark(ctx, 0);
     hipLaunchKernelGGL(brute_nn_kernel, grid, dim3(256), 0, ctx->stream, (const double*)idx->mfma_a, (const pcr_pt*)idx->plain,
@@ -539,8 +537,8 @@ int pcr_brute_nn1(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int64_t n
     const int grid = (int)((nq + 255) / 256);
     hipLaunchKernelGGL(brute_final_kernel<0>, dim3(grid), dim3(256), 0, ctx->stream, (const brute_res*)sc.res, (pcr_pt*)q, (long long)nq,
                        x ? *x : xi, x ? 1 : 0, (const pcr_pt*)idx->plain, max_d2, gated ? 1 : 0, 0, idx->view.origin[0], idx->view.origin[1],
-                       idx->view.origin[2], d_idx, d_d2, (double*)nullptr, ctx->d_counters + BR_FLAG_COUNT_WORD,
-                       ctx->d_counters + BR_FLAG_SEEN_WORD);
+                       idx->view.origin[2], d_idx, d_d2, (double*)nullptr, pcr_counter(ctx, PCR_CW_BRUTE_FLAGS),
+                       pcr_counter(ctx, PCR_CW_BRUTE_FLAGS, 1));
     PCR_HIP(ctx, hipGetLastError());
     brute_scratch_free(ctx, &sc);
     return PCR_OK;
@@ -560,8 +558,8 @@ int pcr_brute_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq
     pcr_prof_mark(ctx, 2);
     hipLaunchKernelGGL(brute_final_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream, (const brute_res*)sc.res, q, (long long)nq, *x, 1,
                        (const pcr_pt*)idx->plain, max_d2, gated ? 1 : 0, write_back, idx->view.origin[0], idx->view.origin[1],
-                       idx->view.origin[2], (int*)nullptr, (double*)nullptr, ctx->d_partials, ctx->d_counters + BR_FLAG_COUNT_WORD,
-                       ctx->d_counters + BR_FLAG_SEEN_WORD);
+                       idx->view.origin[2], (int*)nullptr, (double*)nullptr, ctx->d_partials, pcr_counter(ctx, PCR_CW_BRUTE_FLAGS),
+                       pcr_counter(ctx, PCR_CW_BRUTE_FLAGS, 1));
     pcr_prof_mark(ctx, 3);
     hipLaunchKernelGGL(brute_reduce_partials_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const double*)ctx->d_partials, grid, d_moments);
     pcr_prof_mark(ctx, 4);
@@ -573,5 +571,5 @@ int pcr_brute_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq
 
 // diagnostics (tests, bench): queries the last brute-force search sent to the exact fallback
 int pcr_brute_last_fallback(pcr_ctx* ctx, unsigned int* out) {
-    return pcr_d2h_small(ctx, out, ctx->d_counters + BR_FLAG_SEEN_WORD, sizeof(unsigned int));
+    return pcr_d2h_small(ctx, out, pcr_counter(ctx, PCR_CW_BRUTE_FLAGS, 1), sizeof(unsigned int));
 }

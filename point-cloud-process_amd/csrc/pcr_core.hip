@@ -1,4 +1,5 @@
 // Context, device memory, cloud upload/download/transform, timers.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -7,6 +8,8 @@
 #include <thread>
 #include <atomic>
 #include <memory>
+#include <utility>
+#include <vector>
 #include "pcr_internal.h"
 
 extern "C" {
@@ -597,12 +600,12 @@ static int upload_impl(pcr_ctx* ctx, const S* xyz, int64_t n, int64_t stride, pc
     const auto t_1 = std::chrono::steady_clock::now();
     int block = 256;
     int grid = (int)((n + block - 1) / block);
-    // bounding box: d_counters words 16..29 (six 64-bit maxima + ticket, zero between uploads) -> h_pinned bytes 512..559
+    // bounding box: the PCR_CW_BOX words of d_counters (six 64-bit maxima + ticket, zero between uploads) -> h_pinned bytes 512..559
     unsigned long long* const h_box = (unsigned long long*)((char*)ctx->h_pinned + 512);
     unsigned long long* h_box_dev = nullptr;
     PCR_HIP(ctx, hipHostGetDevicePointer((void**)&h_box_dev, h_box, 0));
     hipLaunchKernelGGL(expand_cloud_kernel<S>, dim3(grid), dim3(block), 0, ctx->stream, d_src, (long long)n, (long long)stride, c->d,
-                       (unsigned long long*)(ctx->d_counters + 16), h_box_dev);
+                       (unsigned long long*)pcr_counter(ctx, PCR_CW_BOX), h_box_dev);
     PCR_HIP(ctx, hipGetLastError());
     // the staging buffer is reused by the next upload (and an unstaged copy reads caller-owned memory): finish before returning
     PCR_HIP(ctx, pcr_sync(ctx->stream));
@@ -644,6 +647,35 @@ int pcr_cloud_rows(pcr_ctx* ctx, const pcr_cloud* c, pcr_pt* d_out) {
     return PCR_OK;
 }
 
+// `rows` holds m caller rows in ascending order, `slot` where each goes in `out` (null: its place in `rows`).  Every record looks its
+// id up; a row listed several times is written to each of its slots.  The ids of a cloud are a permutation of [0, n) (uploads,
+// prepared clouds, the outputs of ground segmentation), so every listed row is written; `out` is untouched elsewhere.
+__global__ void __launch_bounds__(256)
+cloud_gather_rows_kernel(const pcr_pt* __restrict__ pts, long long n, const long long* __restrict__ rows, const long long* __restrict__ slot, int m,
+                         double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const pcr_pt r = pts[i];
+    int lo = 0, hi = m;   // first position whose row is >= id
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (rows[mid] < r.id) lo = mid + 1; else hi = mid;
+    }
+    for (; lo < m && rows[lo] == r.id; ++lo) {
+        const long long s = slot ? slot[lo] : lo;
+        out[3 * s] = r.x; out[3 * s + 1] = r.y; out[3 * s + 2] = r.z;
+    }
+}
+
+int pcr_cloud_gather_rows(pcr_ctx* ctx, const pcr_cloud* c, const long long* d_rows_sorted, const long long* d_slot, int64_t m, double* d_xyz_out) {
+    hipLaunchKernelGGL(cloud_gather_rows_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (long long)c->n,
+                       d_rows_sorted, d_slot, (int)m, d_xyz_out);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
+constexpr int64_t PCR_DOWNLOAD_MAX_ROWS = 4096;   // pcr_cloud_download_rows: rows per call
+
 extern "C" {
 
 int pcr_cloud_upload_f32(pcr_ctx* ctx, const float* xyz, int64_t n, int64_t stride, pcr_cloud** out) {
@@ -668,6 +700,28 @@ int pcr_cloud_download_f64(pcr_ctx* ctx, const pcr_cloud* c, double* out) {
     PCR_HIP(ctx, pcr_sync(ctx->stream));
     pcr_dev_free(ctx, d_tmp, sizeof(double) * 3 * c->n);
     return PCR_OK;
+}
+
+int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows, int64_t m, double* xyz_out) {
+    if (!ctx || !cloud || !rows || !xyz_out || m < 0 || m > PCR_DOWNLOAD_MAX_ROWS) return PCR_E_INVALID;
+    if (m == 0) return PCR_OK;
+    const int64_t n = cloud->n;
+    std::vector<std::pair<long long, long long>> order((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        if (rows[i] < 0 || rows[i] >= n) return PCR_E_INVALID;
+        order[(size_t)i] = {(long long)rows[i], (long long)i};
+    }
+    std::sort(order.begin(), order.end());
+    std::vector<long long> packed(2 * (size_t)m);
+    for (int64_t i = 0; i < m; ++i) { packed[(size_t)i] = order[(size_t)i].first; packed[(size_t)(m + i)] = order[(size_t)i].second; }
+    hipSetDevice(ctx->device);
+    pcr_dev_block d_rows(ctx), d_out(ctx);
+    int rc;
+    if ((rc = d_rows.alloc(sizeof(long long) * 2 * m)) || (rc = d_out.alloc(sizeof(double) * 3 * m))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(d_rows.p, packed.data(), sizeof(long long) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemsetAsync(d_out.p, 0xff, sizeof(double) * 3 * m, ctx->stream));   // NaN: a row no record carries as its id
+    if ((rc = pcr_cloud_gather_rows(ctx, cloud, d_rows.as<long long>(), d_rows.as<long long>() + m, m, d_out.as<double>()))) return rc;
+    return pcr_d2h_small(ctx, xyz_out, d_out.p, sizeof(double) * 3 * m);
 }
 
 int64_t pcr_cloud_size(const pcr_cloud* c) { return c ? c->n : 0; }

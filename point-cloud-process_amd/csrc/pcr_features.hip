@@ -431,7 +431,7 @@ fpfh_scans_kernel(scans_view V, long long ng, int max_nn, const double* __restri
 
 // ------------------------------------------------------------------ host side
 namespace {
-int* fail_word(pcr_ctx* ctx) { return (int*)(ctx->d_counters + 116); }
+int* fail_word(pcr_ctx* ctx) { return (int*)pcr_counter(ctx, PCR_CW_FEATURES_FAIL); }
 
 // A cloud of a few thousand points (what the 2 m down-sample of main.py:35 leaves of a scan: 300 - 1 500 points) is searched without
 // an index: two grid builds per scan -- one per radius, ~20 launches each -- cost several times what the neighbourhoods themselves
@@ -502,7 +502,7 @@ int pcr_fpfh_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_normal
 }
 
 int pcr_scans_features(pcr_ctx* ctx, const scans_view& V, size_t ng, const pcr_global_params* g, const scans_scratch& w, double* d_fpfh) {
-    unsigned int* const redo_n = ctx->d_counters + 117;   // [0]: normals, [1]: SPFH (zero between calls)
+    unsigned int* const redo_n = pcr_counter(ctx, PCR_CW_FEATURES_REDO);   // [0]: normals, [1]: SPFH (zero between calls)
     const unsigned fixed = (unsigned)(ng < (size_t)(16 * ctx->cu_count) ? ng : (size_t)(16 * ctx->cu_count));
     const unsigned int* const none = nullptr;
     if (hipMemsetAsync(redo_n, 0, 8, ctx->stream) != hipSuccess) return PCR_E_HIP;

@@ -20,19 +20,19 @@
 #include <cstring>
 #include <vector>
 #include "pcr_internal.h"
-#include "pcr_grid_dev.h"
+#include "pcr_stream_fit.h"
+#include "pcr_wave.h"
 
 namespace {
 
 constexpr int GM_MAX_K = PCR_GMM_MAX_K;
-constexpr int GM_BLOCK = 256;
+constexpr int GM_BLOCK = PCR_STREAM_BLOCK;
 constexpr int GM_PTS = 4;                        // points per lane, in registers while the components go by
 constexpr int GM_TILE = GM_PTS * GM_BLOCK;       // points per block: the block count is ceil(n / GM_TILE)
 constexpr int GM_CHUNK = 8;                      // components per chunk of the E pass: 8 x (1 + dim) accumulators per lane
 constexpr int GM_CHUNK_COV = 4;                  // of the covariance pass: 4 x 6
 constexpr int GM_NC = 10;                        // doubles per component's constants
 constexpr int GM_NSUM_MAX = GM_MAX_K * 6;        // sums per block slab: cov pass K * 6 (dim 3); E pass K * (1 + dim) + 1 <= 129
-constexpr int GM_TICKET_WORD = 88;               // word of ctx->d_counters (zero at context creation, re-armed by the last block)
 constexpr int GM_ITERS_PER_SYNC = 8;             // EM iterations enqueued per read-back of the loop state's head
 constexpr double GM_LOG_2PI = 1.8378770664093454835606594728112;
 
@@ -128,25 +128,15 @@ __global__ void __launch_bounds__(64) gmm_init_kernel(gmm_state* __restrict__ st
         if (s_bad[j]) { st->status = PCR_E_SINGULAR; st->stop = 1; st->bad_component = j; st->bad_iter = 0; return; }
 }
 
-// block_slab_sums (pcr_grid_dev.h) with plain binary64 adds: one slab per block, the last block's fixed-order total in s_tot
+// block_slab_sums (pcr_wave.h) with plain binary64 adds: one slab per block, the last block's fixed-order total in s_tot
 __device__ inline bool gmm_block_sums(const double (*s_part)[GM_NSUM_MAX], int nsum, double* __restrict__ partials, unsigned int* __restrict__ ticket,
                                       double (*s_red)[GM_NSUM_MAX], double* s_tot) {
     return block_slab_sums<GM_NSUM_MAX>(s_part, nsum, partials, ticket, s_red, s_tot, [](double x, double y, int) { return x + y; });
 }
 
-// the block's tile: GM_PTS points per lane (zeros behind the end), and the constants in LDS
-__device__ inline void gmm_load_tile(const pcr_pt* __restrict__ pts, long long n, const gmm_state* __restrict__ st, int K, double* s_comp, double* x,
-                                     double* y, double* z, bool* valid, long long* id) {
+// the constants of `st` into LDS (every pass, ahead of its tile load and the barrier)
+__device__ inline void gmm_stage_comp(const gmm_state* __restrict__ st, int K, double* s_comp) {
     for (int t = threadIdx.x; t < K * GM_NC; t += GM_BLOCK) s_comp[t] = st->comp[t];
-#pragma unroll
-    for (int p = 0; p < GM_PTS; ++p) {
-        const long long i = ((long long)blockIdx.x * GM_PTS + p) * GM_BLOCK + threadIdx.x;
-        valid[p] = i < n;
-        x[p] = y[p] = z[p] = 0.0;
-        if (id) id[p] = 0;
-        if (valid[p]) { const pcr_pt r = pts[i]; x[p] = r.x; y[p] = r.y; z[p] = r.z; if (id) id[p] = r.id; }
-    }
-    __syncthreads();
 }
 
 // E pass.  Slab layout: component k at [k * (1 + DIM), ...) = N_k, sum gamma x (, y, z); the log-likelihood at K * (1 + DIM).
@@ -160,7 +150,9 @@ gmm_estep_kernel(const pcr_pt* __restrict__ pts, long long n, int K, gmm_state* 
     if (st->stop) return;
     double x[GM_PTS], y[GM_PTS], z[GM_PTS], m[GM_PTS], s[GM_PTS];
     bool valid[GM_PTS];
-    gmm_load_tile(pts, n, st, K, s_comp, x, y, z, valid, nullptr);
+    gmm_stage_comp(st, K, s_comp);
+    block_tile_load<GM_PTS, false>(pts, n, x, y, z, valid, nullptr);
+    __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double ll = 0.0;
 #pragma unroll
@@ -243,7 +235,9 @@ gmm_cov_kernel(const pcr_pt* __restrict__ pts, long long n, int K, gmm_state* __
     double x[GM_PTS], y[GM_PTS], z[GM_PTS], m[GM_PTS], s[GM_PTS];
     bool valid[GM_PTS];
     for (int t = threadIdx.x; t < K * 3; t += GM_BLOCK) s_mean[t] = st->new_mean[t];
-    gmm_load_tile(pts, n, st, K, s_comp, x, y, z, valid, nullptr);
+    gmm_stage_comp(st, K, s_comp);
+    block_tile_load<GM_PTS, false>(pts, n, x, y, z, valid, nullptr);
+    __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int p = 0; p < GM_PTS; ++p) {
@@ -325,15 +319,17 @@ gmm_cov_kernel(const pcr_pt* __restrict__ pts, long long n, int K, gmm_state* __
 // row); the log-likelihood through the slabs like the E pass (one sum)
 template <int DIM>
 __global__ void __launch_bounds__(GM_BLOCK)
-gmm_predict_kernel(const pcr_pt* __restrict__ pts, long long n, int K, gmm_state* __restrict__ st, int* __restrict__ labels, double* __restrict__ resp,
-                   double* __restrict__ partials, unsigned int* __restrict__ ticket) {
+gmm_predict_kernel(const pcr_pt* __restrict__ pts, long long n, int K, gmm_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket,
+                   int* __restrict__ labels, double* __restrict__ resp) {
     __shared__ double s_comp[GM_MAX_K * GM_NC];
     __shared__ double s_part[4][GM_NSUM_MAX], s_red[8][GM_NSUM_MAX], s_tot[GM_NSUM_MAX];
     if (st->stop) return;
     double x[GM_PTS], y[GM_PTS], z[GM_PTS];
     long long id[GM_PTS];
     bool valid[GM_PTS];
-    gmm_load_tile(pts, n, st, K, s_comp, x, y, z, valid, id);
+    gmm_stage_comp(st, K, s_comp);
+    block_tile_load<GM_PTS, true>(pts, n, x, y, z, valid, id);
+    __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double ll = 0.0;
 #pragma unroll
@@ -385,43 +381,17 @@ void state_to_host(const gmm_state* h, int k, int dim, double* means, double* co
     }
 }
 
-struct gmm_run {
-    pcr_ctx* ctx;
-    const pcr_cloud* cloud;
-    int k, dim;
-    unsigned int grid;
-    pcr_dev_block st;
-    explicit gmm_run(pcr_ctx* c) : ctx(c), st(c) {}
-    gmm_state* d_st() const { return st.as<gmm_state>(); }
-    unsigned int* ticket() const { return ctx->d_counters + GM_TICKET_WORD; }
-};
-
 // state uploaded and the constants built; the slabs sized for the largest pass
-int gmm_begin(gmm_run* r, const pcr_cloud* cloud, int k, int dim, const gmm_state* h) {
+int gmm_begin(pcr_stream_fit* r, const pcr_cloud* cloud, int k, int dim, const gmm_state* h) {
     pcr_ctx* ctx = r->ctx;
-    r->cloud = cloud; r->k = k; r->dim = dim;
-    r->grid = (unsigned int)((cloud->n + GM_TILE - 1) / GM_TILE);
     int rc;
-    if ((rc = r->st.alloc(sizeof(gmm_state))) || (rc = pcr_ensure_scratch(ctx, sizeof(double) * GM_NSUM_MAX * (size_t)r->grid))) return rc;
-    PCR_HIP(ctx, hipMemcpyAsync(r->st.p, h, sizeof(gmm_state), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(gmm_init_kernel, dim3(1), dim3(64), 0, ctx->stream, r->d_st(), k, dim);
+    if ((rc = pcr_stream_begin(r, cloud, k, dim, GM_TILE, PCR_CW_GMM_TICKET, h, sizeof(gmm_state), GM_NSUM_MAX))) return rc;
+    hipLaunchKernelGGL(gmm_init_kernel, dim3(1), dim3(64), 0, ctx->stream, r->st.as<gmm_state>(), k, dim);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
-int gmm_estep(gmm_run* r, double* d_hist) {
-    pcr_ctx* ctx = r->ctx;
-    if (r->dim == 3) hipLaunchKernelGGL(gmm_estep_kernel<3>, dim3(r->grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket(), d_hist);
-    else hipLaunchKernelGGL(gmm_estep_kernel<2>, dim3(r->grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket(), d_hist);
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
-}
-int gmm_cov(gmm_run* r) {
-    pcr_ctx* ctx = r->ctx;
-    if (r->dim == 3) hipLaunchKernelGGL(gmm_cov_kernel<3>, dim3(r->grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket());
-    else hipLaunchKernelGGL(gmm_cov_kernel<2>, dim3(r->grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket());
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
-}
+int gmm_estep(pcr_stream_fit* r, double* d_hist) { return pcr_stream_launch(r, gmm_estep_kernel<2>, gmm_estep_kernel<3>, d_hist); }
+int gmm_cov(pcr_stream_fit* r) { return pcr_stream_launch(r, gmm_cov_kernel<2>, gmm_cov_kernel<3>); }
 
 }  // namespace
 
@@ -452,7 +422,7 @@ int pcr_gmm_step(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const dou
     hipSetDevice(ctx->device);
     std::vector<gmm_state> h(1);
     state_from_host(&h[0], k, dim, means, covs, weights, cloud->n);
-    gmm_run r(ctx);
+    pcr_stream_fit r(ctx);
     int rc;
     if ((rc = gmm_begin(&r, cloud, k, dim, &h[0])) || (rc = gmm_estep(&r, nullptr)) || (rc = gmm_cov(&r))) return rc;
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, sizeof(gmm_state)))) return rc;
@@ -481,7 +451,7 @@ int pcr_gmm_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_gmm_params* para
     h[0].loop = 1;
     h[0].max_iter = max_iter;
     h[0].tol = params->tol;
-    gmm_run r(ctx);
+    pcr_stream_fit r(ctx);
     pcr_dev_block d_hist(ctx);
     int rc;
     if ((rc = d_hist.alloc(sizeof(double) * max_iter))) return rc;
@@ -489,15 +459,11 @@ int pcr_gmm_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_gmm_params* para
     if ((rc = gmm_begin(&r, cloud, k, dim, &h[0]))) return rc;
     // iteration i = E pass + covariance pass; the stop after iteration i is decided in the E pass of iteration i + 1, so a loop of
     // `iters` iterations costs 2 iters + 1 passes.  Passes behind a stop return at once.
-    gmm_state head;
-    for (int i = 0; i <= max_iter; ++i) {
-        if ((rc = gmm_estep(&r, d_hist.as<double>()))) return rc;
-        if (i < max_iter && (rc = gmm_cov(&r))) return rc;
-        if (i == max_iter || (i + 1) % GM_ITERS_PER_SYNC == 0) {
-            if ((rc = pcr_d2h_small(ctx, &head, r.st.p, GM_HEAD_BYTES))) return rc;
-            if (head.stop) break;
-        }
-    }
+    if ((rc = pcr_stream_loop(&r, max_iter + 1, GM_ITERS_PER_SYNC, GM_HEAD_BYTES, [&](int i) {
+            const int e = gmm_estep(&r, d_hist.as<double>());
+            return (e || i == max_iter) ? e : gmm_cov(&r);
+        })))
+        return rc;
     PCR_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, sizeof(gmm_state)))) return rc;
     result->iters = h[0].it;
@@ -513,10 +479,7 @@ int pcr_gmm_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_gmm_params* para
             PCR_HIP(ctx, pcr_sync(ctx->stream));
         }
     }
-    PCR_HIP(ctx, pcr_event_sync(ctx->ev1));
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    result->device_ms = ms;
+    if ((rc = pcr_events_ms(ctx, &result->device_ms))) return rc;
     return h[0].status;
 }
 
@@ -528,14 +491,12 @@ int pcr_gmm_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const 
     hipSetDevice(ctx->device);
     std::vector<gmm_state> h(1);
     state_from_host(&h[0], k, dim, means, covs, weights, n);
-    gmm_run r(ctx);
+    pcr_stream_fit r(ctx);
     pcr_dev_block d_labels(ctx), d_resp(ctx);
     int rc;
     if ((rc = d_labels.alloc(sizeof(int32_t) * n)) || (resp_out && (rc = d_resp.alloc(sizeof(double) * n * k)))) return rc;
     if ((rc = gmm_begin(&r, cloud, k, dim, &h[0]))) return rc;
-    if (dim == 3) hipLaunchKernelGGL(gmm_predict_kernel<3>, dim3(r.grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)cloud->d, (long long)n, k, r.d_st(), d_labels.as<int>(), d_resp.as<double>(), ctx->d_partials, r.ticket());
-    else hipLaunchKernelGGL(gmm_predict_kernel<2>, dim3(r.grid), dim3(GM_BLOCK), 0, ctx->stream, (const pcr_pt*)cloud->d, (long long)n, k, r.d_st(), d_labels.as<int>(), d_resp.as<double>(), ctx->d_partials, r.ticket());
-    PCR_HIP(ctx, hipGetLastError());
+    if ((rc = pcr_stream_launch(&r, gmm_predict_kernel<2>, gmm_predict_kernel<3>, d_labels.as<int>(), d_resp.as<double>()))) return rc;
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, GM_HEAD_BYTES))) return rc;
     if (h[0].status != PCR_OK) return h[0].status;
     if (loglik_out) *loglik_out = h[0].loglik;

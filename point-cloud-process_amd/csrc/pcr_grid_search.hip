@@ -1721,7 +1721,9 @@ grid_accumulate_kernel(pcr_grid_view gv, const pcr_pt* __restrict__ q, long long
     }
     // ---- the block that arrives last sums the slabs in fixed order (saves a launch boundary).
     // Hand-off per the CDNA4 recipe: drained stores -> barrier -> agent-scope release -> ticket;
-    // last arriver: agent-scope acquire -> barrier -> plain loads.
+    // last arriver: agent-scope acquire -> barrier -> plain loads.  Deliberately NOT block_slab_sums (pcr_wave.h), which is this
+    // recipe for everybody else: this kernel is on the benchmarked ICP path, resets the hard counters between ticket and sum and
+    // batches its slab loads eight wide.
     __shared__ unsigned int s_last;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1876,7 +1878,7 @@ int pcr_grid_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     // after a write-back pass the cloud already holds the transformed points
     pcr_prof_mark(ctx, 2);
     hipLaunchKernelGGL(grid_accumulate_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (const pcr_pt*)qc->d, (long long)nq, *x,
-                       write_back ? 0 : 1, (const unsigned int*)sc.res_pos.p, max_d2, gated ? 1 : 0, ctx->d_partials, ctx->d_counters + 64,
+                       write_back ? 0 : 1, (const unsigned int*)sc.res_pos.p, max_d2, gated ? 1 : 0, ctx->d_partials, pcr_counter(ctx, PCR_CW_ICP_TICKET),
                        d_moments, sc.hard_count, (pcr_icp_dev_state*)nullptr, pcr_icp_loop_args{}, (wt_xyz*)nullptr);
     pcr_prof_mark(ctx, 3);
     pcr_prof_mark(ctx, 4);
@@ -2057,7 +2059,7 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
                 if (rc) break;
                 pcr_prof_mark(ctx, 2);
                 hipLaunchKernelGGL(grid_accumulate_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (const pcr_pt*)qc->d, (long long)nq, xi,
-                                   0, (const unsigned int*)sc.res_pos.p, params->max_d2, gated ? 1 : 0, ctx->d_partials, ctx->d_counters + 64,
+                                   0, (const unsigned int*)sc.res_pos.p, params->max_d2, gated ? 1 : 0, ctx->d_partials, pcr_counter(ctx, PCR_CW_ICP_TICKET),
                                    (double*)nullptr, sc.hard_count, d_st, la, sc.prev_xyz.as<wt_xyz>());
             }
             pcr_prof_mark(ctx, 3);

@@ -4,8 +4,8 @@
 // every hypothesis is known up front and the reference's sequential loop becomes: score ALL hypotheses in one streaming pass, then
 // apply its running-best / early-break rule (clustering.py:75-81) to the counts.  Launches, all on the context's stream with no host
 // round trip before the counts are final and the winner is masked:
-//   ground_fetch_kernel   (Morton-reordered clouds only) the sampled records by caller row: position != row there, so every record
-//                         looks its id up in the sorted list of distinct sampled rows;
+//   pcr_cloud_gather_rows (Morton-reordered clouds only) the sampled points by caller row: position != row there, so every record
+//                         looks its id up in the sorted list of distinct sampled rows (pcr_core.hip);
 //   ground_setup_kernel   p0 and the unit normal of every hypothesis (pcr_ground_plane_from), counters zeroed;
 //   ground_score_kernel   one launch per chunk of GR_CHUNK hypotheses (the default 35 are one): 32 B per point read once, the chunk's
 //                         planes broadcast from LDS, per wave one integer count per hypothesis (popcount of the wave's ballots, scalar
@@ -19,14 +19,14 @@
 #include <cstring>
 #include <vector>
 #include "pcr_internal.h"
+#include "pcr_wave.h"
 
 namespace {
 
 constexpr int GR_CHUNK = 256;       // hypotheses per scoring launch: their planes and counters sit in LDS (13 KiB)
 constexpr int GR_PTS = 4;           // points per lane of the scoring pass, in registers while the chunk's planes go by
-constexpr int GR_BLOCK = 256;
+constexpr int GR_BLOCK = PCR_STREAM_BLOCK;
 constexpr int GR_TILE = 1024;       // rows per block of the compaction scan (4 per thread)
-constexpr int GR_TICKET_WORD = 80;  // word of ctx->d_counters (zero at context creation, re-armed by the block that takes the last ticket)
 
 struct gr_plane { double p[3], n[3]; };   // p0 and unit normal (NaN for a degenerate triple, clustering.py:61-62)
 
@@ -77,27 +77,9 @@ __host__ __device__ inline int ground_select_rule(Load count_of, int32_t n_hyp, 
     return best < 0 ? PCR_E_TOO_FEW_ASSOC : PCR_OK;   // every hypothesis degenerate: the reference indexes with None (clustering.py:83)
 }
 
-// position of `row` in the ascending list urows[0..nu), or -1
-__device__ inline int gr_find_row(const long long* __restrict__ urows, int nu, long long row) {
-    int lo = 0, hi = nu;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (urows[mid] < row) lo = mid + 1; else hi = mid;
-    }
-    return (lo < nu && urows[lo] == row) ? lo : -1;
-}
-
+// slot_u[3h + s]: which distinct sampled row trial h's sample s is.  uxyz != null: the gathered points; else position = row.
 __global__ void __launch_bounds__(GR_BLOCK)
-ground_fetch_kernel(const pcr_pt* __restrict__ pts, long long n, const long long* __restrict__ urows, int nu, pcr_pt* __restrict__ upts) {
-    const long long i = (long long)blockIdx.x * GR_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const int u = gr_find_row(urows, nu, pts[i].id);
-    if (u >= 0) upts[u] = pts[i];
-}
-
-// slot_u[3h + s]: which distinct sampled row trial h's sample s is.  upts != null: the fetched records; else position = row.
-__global__ void __launch_bounds__(GR_BLOCK)
-ground_setup_kernel(const pcr_pt* __restrict__ pts, const pcr_pt* __restrict__ upts, const long long* __restrict__ urows, const int* __restrict__ slot_u,
+ground_setup_kernel(const pcr_pt* __restrict__ pts, const double* __restrict__ uxyz, const long long* __restrict__ urows, const int* __restrict__ slot_u,
                     int n_hyp, gr_plane* __restrict__ planes, unsigned long long* __restrict__ counts, gr_state* __restrict__ st) {
     const int h = blockIdx.x * GR_BLOCK + threadIdx.x;
     if (h == 0) {
@@ -109,8 +91,8 @@ ground_setup_kernel(const pcr_pt* __restrict__ pts, const pcr_pt* __restrict__ u
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
         const int u = slot_u[3 * h + s];
-        const pcr_pt r = upts ? upts[u] : pts[urows[u]];
-        p[s][0] = r.x; p[s][1] = r.y; p[s][2] = r.z;
+        if (uxyz) { p[s][0] = uxyz[3 * u]; p[s][1] = uxyz[3 * u + 1]; p[s][2] = uxyz[3 * u + 2]; }
+        else { const pcr_pt r = pts[urows[u]]; p[s][0] = r.x; p[s][1] = r.y; p[s][2] = r.z; }
     }
     planes[h] = pcr_ground_plane_from(p[0], p[1], p[2]);
     counts[h] = 0ull;
@@ -134,13 +116,7 @@ ground_score_kernel(const pcr_pt* __restrict__ pts, long long n, const gr_plane*
     for (int t = threadIdx.x; t < nh; t += GR_BLOCK) s_cnt[t] = 0u;
     double x[GR_PTS], y[GR_PTS], z[GR_PTS];
     bool valid[GR_PTS];
-#pragma unroll
-    for (int k = 0; k < GR_PTS; ++k) {
-        const long long i = ((long long)blockIdx.x * GR_PTS + k) * GR_BLOCK + threadIdx.x;
-        valid[k] = i < n;
-        x[k] = y[k] = z[k] = 0.0;
-        if (valid[k]) { const pcr_pt p = pts[i]; x[k] = p.x; y[k] = p.y; z[k] = p.z; }
-    }
+    block_tile_load<GR_PTS, false>(pts, n, x, y, z, valid, nullptr);
     __syncthreads();
     const bool first_lane = (threadIdx.x & 63) == 0;
     for (int h = 0; h < nh; ++h) {
@@ -212,13 +188,8 @@ ground_scan_kernel(const unsigned char* __restrict__ flag, long long n, const gr
         o[k] = (r0 + k < n && flag[r0 + k] == 0) ? 1u : 0u;
         mine += o[k];
     }
-    unsigned int inc = mine;   // inclusive scan across the wave
+    const unsigned int inc = wave_incl_scan_add(mine);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int up = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += up;
-    }
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     unsigned int before = inc - mine;
@@ -243,12 +214,7 @@ ground_offsets_kernel(unsigned int* __restrict__ tile_sum, long long n_tiles, gr
     for (long long base = 0; base < n_tiles; base += GR_BLOCK) {
         const long long t = base + threadIdx.x;
         const unsigned int mine = t < n_tiles ? tile_sum[t] : 0u;
-        unsigned int inc = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned int up = __shfl_up(inc, d, 64);
-            if (lane >= d) inc += up;
-        }
+        const unsigned int inc = wave_incl_scan_add(mine);
         if (lane == 63) s_wave[wave] = inc;
         __syncthreads();
         unsigned long long before = s_carry + (inc - mine);
@@ -320,12 +286,12 @@ int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
 
     const long long n_tiles = (n + GR_TILE - 1) / GR_TILE;
     const bool want_compact = outliers_out || outlier_rows_out;
-    pcr_dev_block b_urows(ctx), b_slot(ctx), b_upts(ctx), b_planes(ctx), b_counts(ctx), b_state(ctx), b_flag(ctx), b_pre(ctx), b_tiles(ctx), b_rows(ctx);
+    pcr_dev_block b_urows(ctx), b_slot(ctx), b_uxyz(ctx), b_planes(ctx), b_counts(ctx), b_state(ctx), b_flag(ctx), b_pre(ctx), b_tiles(ctx), b_rows(ctx);
     int rc;
     if ((rc = b_urows.alloc(sizeof(long long) * nu)) || (rc = b_slot.alloc(sizeof(int) * n_slots)) || (rc = b_planes.alloc(sizeof(gr_plane) * n_hyp)) ||
         (rc = b_counts.alloc(sizeof(unsigned long long) * n_hyp)) || (rc = b_state.alloc(sizeof(gr_state))) || (rc = b_flag.alloc((size_t)n)))
         return rc;
-    if (cloud->morton_sorted && (rc = b_upts.alloc(sizeof(pcr_pt) * nu))) return rc;
+    if (cloud->morton_sorted && (rc = b_uxyz.alloc(sizeof(double) * 3 * nu))) return rc;
     if (want_compact && ((rc = b_pre.alloc(sizeof(unsigned int) * n)) || (rc = b_tiles.alloc(sizeof(unsigned int) * n_tiles)))) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(b_urows.p, urows.data(), sizeof(long long) * nu, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemcpyAsync(b_slot.p, slot_u.data(), sizeof(int) * n_slots, hipMemcpyHostToDevice, ctx->stream));
@@ -334,18 +300,15 @@ int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
     gr_state* d_st = b_state.as<gr_state>();
     unsigned long long* d_counts = b_counts.as<unsigned long long>();
     const unsigned int grid_n = (unsigned int)((n + GR_BLOCK - 1) / GR_BLOCK);
-    if (cloud->morton_sorted) {
-        hipLaunchKernelGGL(ground_fetch_kernel, dim3(grid_n), dim3(GR_BLOCK), 0, ctx->stream, pts, n, b_urows.as<const long long>(), nu, b_upts.as<pcr_pt>());
-        PCR_HIP(ctx, hipGetLastError());
-    }
+    if (cloud->morton_sorted && (rc = pcr_cloud_gather_rows(ctx, cloud, b_urows.as<const long long>(), nullptr, nu, b_uxyz.as<double>()))) return rc;
     hipLaunchKernelGGL(ground_setup_kernel, dim3((unsigned int)((n_hyp + GR_BLOCK - 1) / GR_BLOCK)), dim3(GR_BLOCK), 0, ctx->stream, pts,
-                       (const pcr_pt*)b_upts.p, b_urows.as<const long long>(), b_slot.as<const int>(), n_hyp, b_planes.as<gr_plane>(), d_counts, d_st);
+                       (const double*)b_uxyz.p, b_urows.as<const long long>(), b_slot.as<const int>(), n_hyp, b_planes.as<gr_plane>(), d_counts, d_st);
     PCR_HIP(ctx, hipGetLastError());
     const unsigned int grid_score = (unsigned int)((n + GR_PTS * GR_BLOCK - 1) / (GR_PTS * GR_BLOCK));
     for (int h0 = 0; h0 < n_hyp; h0 += GR_CHUNK) {
         const int nh = std::min(GR_CHUNK, n_hyp - h0);
         hipLaunchKernelGGL(ground_score_kernel, dim3(grid_score), dim3(GR_BLOCK), 0, ctx->stream, pts, n, b_planes.as<const gr_plane>(), h0, nh, params->tau,
-                           d_counts, ctx->d_counters + GR_TICKET_WORD, h0 + nh >= n_hyp ? 1 : 0, n_hyp, params->ratio, d_st);
+                           d_counts, pcr_counter(ctx, PCR_CW_GROUND_TICKET), h0 + nh >= n_hyp ? 1 : 0, n_hyp, params->ratio, d_st);
         PCR_HIP(ctx, hipGetLastError());
     }
     hipLaunchKernelGGL(ground_mask_kernel, dim3(grid_n), dim3(GR_BLOCK), 0, ctx->stream, pts, n, params->tau, (const gr_state*)d_st, b_flag.as<unsigned char>());

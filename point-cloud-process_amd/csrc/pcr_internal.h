@@ -180,6 +180,9 @@ PCR_HIDDEN int pcr_dev_alloc(pcr_ctx* ctx, size_t bytes, void** out);
 PCR_HIDDEN void pcr_dev_free(pcr_ctx* ctx, void* p, size_t bytes);
 // records of a cloud in caller row order (the device copy may be Morton-reordered)
 PCR_HIDDEN int pcr_cloud_rows(pcr_ctx* ctx, const pcr_cloud* c, pcr_pt* d_out);
+// the x, y, z of the records that carry the m caller rows of d_rows_sorted (ascending; repeats allowed) -> d_xyz_out[3 * d_slot[j]]
+// (d_slot null: 3 * j), whatever the order of the records: one pass over the cloud, a binary search per record (enqueued, no wait)
+PCR_HIDDEN int pcr_cloud_gather_rows(pcr_ctx* ctx, const pcr_cloud* c, const long long* d_rows_sorted, const long long* d_slot, int64_t m, double* d_xyz_out);
 
 // device scratch that goes back to the context's arena when it leaves scope (every return path, error or not)
 struct pcr_dev_block {
@@ -199,6 +202,51 @@ struct pcr_dev_block {
 // (32 counters, one per 128-byte line)
 constexpr int PCR_HARD_COUNTERS = 1024;
 constexpr size_t PCR_COUNTER_BYTES = 4 * (1024 + 1024);
+// THE table of the small counters: one row per user, {first word, words}, ascending.  All are zero at context creation and every user
+// leaves its words zero (or re-zeroes them before use).  A new user adds a name and a row; rows that overlap, are out of order or
+// missing do not compile.
+enum pcr_cw {
+    PCR_CW_BOX,             // pcr_core: bounding box of an upload, six 64-bit maxima + ticket
+    PCR_CW_VOXEL,           // pcr_voxel: [0] groups, [1] big voxels
+    PCR_CW_ICP_TICKET,      // pcr_grid_search: grid_accumulate_kernel
+    PCR_CW_P2P_TICKET,      // pcr_point2plane
+    PCR_CW_GROUND_TICKET,   // pcr_ground
+    PCR_CW_GMM_TICKET,      // pcr_gmm
+    PCR_CW_KMEANS_TICKET,   // pcr_kmeans
+    PCR_CW_NORMALS_REDO,    // pcr_normals: points left for the second pass
+    PCR_CW_FEATURES_FAIL,   // pcr_features: more than 1024 equidistant neighbours
+    PCR_CW_FEATURES_REDO,   // pcr_features: [0] normals, [1] SPFH
+    PCR_CW_BRUTE_FLAGS,     // pcr_brute: [0] flagged queries, [1] those of the last call
+    PCR_CW_ISS_CAND,        // pcr_iss: candidates
+    PCR_CW_KNN_LEFT,        // pcr_knn: queries left by [0] stage 2, [1] the full block scan, [2] stage 1
+    PCR_CW_USERS
+};
+struct pcr_cw_span { int first, words; };
+constexpr pcr_cw_span PCR_CW_SPAN[PCR_CW_USERS] = {
+    {16, 14},   // BOX            16..29
+    {48, 2},    // VOXEL          48..49
+    {64, 1},    // ICP_TICKET
+    {72, 1},    // P2P_TICKET
+    {80, 1},    // GROUND_TICKET
+    {88, 1},    // GMM_TICKET
+    {96, 1},    // KMEANS_TICKET
+    {112, 1},   // NORMALS_REDO
+    {116, 1},   // FEATURES_FAIL
+    {117, 2},   // FEATURES_REDO  117..118
+    {120, 2},   // BRUTE_FLAGS    120..121
+    {124, 1},   // ISS_CAND
+    {125, 3},   // KNN_LEFT       125..127
+};
+constexpr bool pcr_cw_disjoint() {
+    int end = 0;
+    for (int u = 0; u < PCR_CW_USERS; ++u) {
+        if (PCR_CW_SPAN[u].words < 1 || PCR_CW_SPAN[u].first < end) return false;
+        end = PCR_CW_SPAN[u].first + PCR_CW_SPAN[u].words;
+    }
+    return end <= PCR_HARD_COUNTERS;
+}
+static_assert(pcr_cw_disjoint(), "d_counters: two users share a word, or a user has no row");
+static inline unsigned int* pcr_counter(const pcr_ctx* ctx, pcr_cw user, int k = 0) { return ctx->d_counters + PCR_CW_SPAN[user].first + k; }
 PCR_HIDDEN int pcr_ensure_scratch(pcr_ctx* ctx, size_t partial_bytes);
 PCR_HIDDEN void pcr_xform_from_T(const double* T, pcr_xform* x);
 // profile helpers: mark slot boundary k (0..4) on the stream; finish() syncs and accumulates

@@ -241,7 +241,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     const bool dev_nms = want_kp && max_keypoints >= 0 && max_keypoints < ISS_NMS_MAX;   // otherwise the host loop over a heap of the candidates
     int* d_cand = nullptr;
     pcr_dev_block b_rec(ctx), b_rec2(ctx), b_tmp(ctx);
-    unsigned int* d_cand_count = ctx->d_counters + 124;
+    unsigned int* d_cand_count = pcr_counter(ctx, PCR_CW_ISS_CAND);
     if (want_kp) {
         if (dev_nms) { if ((rc = b_rec.alloc(sizeof(iss_cand) * n))) return rc; }
         else if ((rc = pcr_dev_alloc(ctx, sizeof(int) * n, (void**)&d_cand))) return rc;

@@ -12,25 +12,22 @@
 // in ctx->d_partials, and the last block adds the slabs in a fixed order.  Counts are integers all the way (a slab's count slots hold
 // 64-bit integers).  No floating-point atomics, the block count depends on n alone: two runs give the same bits.  Loop state lives on
 // the device; passes enqueued behind a stop are no-ops, and the host reads a 40-byte head once per KM_ITERS_PER_SYNC iterations.
-#include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <utility>
 #include <vector>
 #include "pcr_internal.h"
-#include "pcr_grid_dev.h"
+#include "pcr_stream_fit.h"
+#include "pcr_wave.h"
 
 namespace {
 
 constexpr int KM_MAX_K = PCR_KMEANS_MAX_K;
-constexpr int KM_BLOCK = 256;
+constexpr int KM_BLOCK = PCR_STREAM_BLOCK;
 constexpr int KM_PTS = 4;                        // points per lane, in registers while the clusters go by
 constexpr int KM_TILE = KM_PTS * KM_BLOCK;       // points per block: the block count is ceil(n / KM_TILE)
 constexpr int KM_CHUNK = 8;                      // clusters per chunk: 8 x dim sums and 8 counts per lane
 constexpr int KM_NSUM_MAX = KM_MAX_K * 4 + 1;    // values per block slab: K * (1 + dim) + 1
-constexpr int KM_TICKET_WORD = 96;               // word of ctx->d_counters (zero at context creation, re-armed by the last block)
 constexpr int KM_ITERS_PER_SYNC = 8;             // iterations enqueued per read-back of the loop state's head
-constexpr int KM_MAX_ROWS = 4096;                // pcr_cloud_download_rows: rows per call
 
 // Loop state on the device.  The head (the first 40 bytes) is what the host reads per chunk of iterations.
 struct __attribute__((aligned(16))) km_state {
@@ -59,7 +56,7 @@ __device__ inline double km_d2(const double* c, double x, double y, double z) {
     return d;
 }
 
-// block_slab_sums (pcr_grid_dev.h) with integer adds in the count slots (t < K * nt with t % nt == 0), binary64 adds elsewhere
+// block_slab_sums (pcr_wave.h) with integer adds in the count slots (t < K * nt with t % nt == 0), binary64 adds elsewhere
 __device__ inline bool km_block_sums(const double (*s_part)[KM_NSUM_MAX], int nsum, int K, int nt, double* __restrict__ partials,
                                      unsigned int* __restrict__ ticket, double (*s_red)[KM_NSUM_MAX], double* s_tot) {
     return block_slab_sums<KM_NSUM_MAX>(s_part, nsum, partials, ticket, s_red, s_tot, [K, nt](double x, double y, int t) {
@@ -78,13 +75,8 @@ __device__ inline void km_tile_pass(const pcr_pt* __restrict__ pts, long long n,
     double x[KM_PTS], y[KM_PTS], z[KM_PTS];
     int lab[KM_PTS];
     long long id[KM_PTS];
-#pragma unroll
-    for (int p = 0; p < KM_PTS; ++p) {
-        const long long i = ((long long)blockIdx.x * KM_PTS + p) * KM_BLOCK + threadIdx.x;
-        x[p] = y[p] = z[p] = 0.0;
-        id[p] = -1;   // behind the end
-        if (i < n) { const pcr_pt r = pts[i]; x[p] = r.x; y[p] = r.y; z[p] = r.z; id[p] = r.id; }
-    }
+    bool valid[KM_PTS];
+    block_tile_load<KM_PTS, true>(pts, n, x, y, z, valid, id);
     __syncthreads();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     double inertia = 0.0;
@@ -96,10 +88,9 @@ __device__ inline void km_tile_pass(const pcr_pt* __restrict__ pts, long long n,
             const double d = km_d2<DIM>(s_c + 3 * k, x[p], y[p], z[p]);
             if (d < best) { best = d; arg = k; }
         }
-        const bool valid = id[p] >= 0;
-        lab[p] = valid ? arg : -1;
-        inertia += valid ? best : 0.0;
-        if (valid && labels) labels[id[p]] = arg;
+        lab[p] = valid[p] ? arg : -1;
+        inertia += valid[p] ? best : 0.0;
+        if (valid[p] && labels) labels[id[p]] = arg;
     }
     inertia = wave_total_f64(inertia);
     if (lane == 63) s_part[wave][K * NT] = inertia;
@@ -192,8 +183,8 @@ kmeans_assign_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_stat
 // inertia under the centres of `st`.  Slab layout: N_k at [k], the inertia at [K].
 template <int DIM>
 __global__ void __launch_bounds__(KM_BLOCK)
-kmeans_label_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_state* __restrict__ st, int* __restrict__ labels, double* __restrict__ partials,
-                    unsigned int* __restrict__ ticket) {
+kmeans_label_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket,
+                    int* __restrict__ labels) {
     __shared__ double s_c[KM_MAX_K * 3];
     __shared__ double s_part[4][KM_NSUM_MAX], s_red[8][KM_NSUM_MAX], s_tot[KM_NSUM_MAX];
     km_tile_pass<DIM, false>(pts, n, K, st, labels, s_c, s_part);
@@ -207,27 +198,6 @@ kmeans_label_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_state
     }
     st->n_empty = n_empty;
     st->inertia = s_tot[K];
-}
-
-// pcr_cloud_download_rows: `rows` holds the m asked rows in ascending order, `slot` where each goes in the caller's list.  Every
-// record looks its id up; a row asked several times is written to each of its slots.  The ids of a cloud are a permutation of
-// [0, n) (uploads, prepared clouds, the outputs of ground segmentation); `out` is NaN-filled beforehand, so a
-// row that no record carried would come back as NaN, never as stale memory.
-__global__ void __launch_bounds__(256)
-cloud_gather_rows_kernel(const pcr_pt* __restrict__ pts, long long n, const long long* __restrict__ rows, const long long* __restrict__ slot, int m,
-                         double* __restrict__ out) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const pcr_pt r = pts[i];
-    int lo = 0, hi = m;   // first position whose row is >= id
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (rows[mid] < r.id) lo = mid + 1; else hi = mid;
-    }
-    for (; lo < m && rows[lo] == r.id; ++lo) {
-        const long long s = slot[lo];
-        out[3 * s] = r.x; out[3 * s + 1] = r.y; out[3 * s + 2] = r.z;
-    }
 }
 
 bool shape_ok(int k, int dim) { return k >= 1 && k <= KM_MAX_K && (dim == 2 || dim == 3); }
@@ -249,41 +219,13 @@ void centers_to_host(const double* c3, int k, int dim, double* out) {
         for (int c = 0; c < dim; ++c) out[j * dim + c] = c3[3 * j + c];
 }
 
-struct km_run {
-    pcr_ctx* ctx;
-    const pcr_cloud* cloud;
-    int k, dim;
-    unsigned int grid;
-    pcr_dev_block st;
-    explicit km_run(pcr_ctx* c) : ctx(c), st(c) {}
-    km_state* d_st() const { return st.as<km_state>(); }
-    unsigned int* ticket() const { return ctx->d_counters + KM_TICKET_WORD; }
-};
-
-// state uploaded, the slabs sized
-int km_begin(km_run* r, const pcr_cloud* cloud, int k, int dim, const km_state* h) {
-    pcr_ctx* ctx = r->ctx;
-    r->cloud = cloud; r->k = k; r->dim = dim;
-    r->grid = (unsigned int)((cloud->n + KM_TILE - 1) / KM_TILE);
-    int rc;
-    if ((rc = r->st.alloc(sizeof(km_state))) || (rc = pcr_ensure_scratch(ctx, sizeof(double) * KM_NSUM_MAX * (size_t)r->grid))) return rc;
-    PCR_HIP(ctx, hipMemcpyAsync(r->st.p, h, sizeof(km_state), hipMemcpyHostToDevice, ctx->stream));
-    return PCR_OK;
+int km_begin(pcr_stream_fit* r, const pcr_cloud* cloud, int k, int dim, const km_state* h) {
+    return pcr_stream_begin(r, cloud, k, dim, KM_TILE, PCR_CW_KMEANS_TICKET, h, sizeof(km_state), KM_NSUM_MAX);
 }
-int km_assign(km_run* r, double* d_inertia_hist, double* d_shift_hist) {
-    pcr_ctx* ctx = r->ctx;
-    if (r->dim == 3) hipLaunchKernelGGL(kmeans_assign_kernel<3>, dim3(r->grid), dim3(KM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket(), d_inertia_hist, d_shift_hist);
-    else hipLaunchKernelGGL(kmeans_assign_kernel<2>, dim3(r->grid), dim3(KM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), ctx->d_partials, r->ticket(), d_inertia_hist, d_shift_hist);
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
+int km_assign(pcr_stream_fit* r, double* d_inertia_hist, double* d_shift_hist) {
+    return pcr_stream_launch(r, kmeans_assign_kernel<2>, kmeans_assign_kernel<3>, d_inertia_hist, d_shift_hist);
 }
-int km_label(km_run* r, int* d_labels) {
-    pcr_ctx* ctx = r->ctx;
-    if (r->dim == 3) hipLaunchKernelGGL(kmeans_label_kernel<3>, dim3(r->grid), dim3(KM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), d_labels, ctx->d_partials, r->ticket());
-    else hipLaunchKernelGGL(kmeans_label_kernel<2>, dim3(r->grid), dim3(KM_BLOCK), 0, ctx->stream, (const pcr_pt*)r->cloud->d, (long long)r->cloud->n, r->k, r->d_st(), d_labels, ctx->d_partials, r->ticket());
-    PCR_HIP(ctx, hipGetLastError());
-    return PCR_OK;
-}
+int km_label(pcr_stream_fit* r, int* d_labels) { return pcr_stream_launch(r, kmeans_label_kernel<2>, kmeans_label_kernel<3>, d_labels); }
 
 }  // namespace
 
@@ -305,7 +247,7 @@ int pcr_kmeans_step(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const 
     hipSetDevice(ctx->device);
     std::vector<km_state> h(1);
     state_from_host(&h[0], k, dim, centers, 1, 0.0);
-    km_run r(ctx);
+    pcr_stream_fit r(ctx);
     int rc;
     if ((rc = km_begin(&r, cloud, k, dim, &h[0])) || (rc = km_assign(&r, nullptr, nullptr))) return rc;
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, sizeof(km_state)))) return rc;
@@ -328,7 +270,7 @@ int pcr_kmeans_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_kmeans_params
     memset(result, 0, sizeof(*result));
     std::vector<km_state> h(1);
     state_from_host(&h[0], k, dim, centers0, max_iter, params->tol);
-    km_run r(ctx);
+    pcr_stream_fit r(ctx);
     pcr_dev_block d_hist(ctx), d_labels(ctx);
     int rc;
     if ((rc = d_hist.alloc(sizeof(double) * 2 * max_iter)) || (labels_out && (rc = d_labels.alloc(sizeof(int32_t) * n)))) return rc;
@@ -337,14 +279,7 @@ int pcr_kmeans_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_kmeans_params
     PCR_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if ((rc = km_begin(&r, cloud, k, dim, &h[0]))) return rc;
     // one pass per iteration; passes behind a stop return at once.  Then the final pass under the final centres.
-    km_state head;
-    for (int i = 0; i < max_iter; ++i) {
-        if ((rc = km_assign(&r, d_inertia_hist, d_shift_hist))) return rc;
-        if (i + 1 == max_iter || (i + 1) % KM_ITERS_PER_SYNC == 0) {
-            if ((rc = pcr_d2h_small(ctx, &head, r.st.p, KM_HEAD_BYTES))) return rc;
-            if (head.stop) break;
-        }
-    }
+    if ((rc = pcr_stream_loop(&r, max_iter, KM_ITERS_PER_SYNC, KM_HEAD_BYTES, [&](int) { return km_assign(&r, d_inertia_hist, d_shift_hist); }))) return rc;
     if ((rc = km_label(&r, d_labels.as<int>()))) return rc;
     PCR_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, sizeof(km_state)))) return rc;
@@ -359,11 +294,7 @@ int pcr_kmeans_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_kmeans_params
     if (shift_hist_out) PCR_HIP(ctx, hipMemcpyAsync(shift_hist_out, d_shift_hist, sizeof(double) * h[0].it, hipMemcpyDeviceToHost, ctx->stream));
     if (inertia_hist_out || shift_hist_out) PCR_HIP(ctx, pcr_sync(ctx->stream));
     if (labels_out && (rc = pcr_d2h_staged(ctx, labels_out, d_labels.p, sizeof(int32_t) * n))) return rc;
-    PCR_HIP(ctx, pcr_event_sync(ctx->ev1));
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    result->device_ms = ms;
-    return PCR_OK;
+    return pcr_events_ms(ctx, &result->device_ms);
 }
 
 int pcr_kmeans_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, const double* centers, int32_t* labels_out, int64_t* counts_out,
@@ -374,7 +305,7 @@ int pcr_kmeans_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, con
     hipSetDevice(ctx->device);
     std::vector<km_state> h(1);
     state_from_host(&h[0], k, dim, centers, 1, 0.0);
-    km_run r(ctx);
+    pcr_stream_fit r(ctx);
     pcr_dev_block d_labels(ctx);
     int rc;
     if ((rc = d_labels.alloc(sizeof(int32_t) * n)) || (rc = km_begin(&r, cloud, k, dim, &h[0])) || (rc = km_label(&r, d_labels.as<int>()))) return rc;
@@ -382,30 +313,6 @@ int pcr_kmeans_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int dim, con
     if (counts_out) for (int j = 0; j < k; ++j) counts_out[j] = h[0].counts[j];
     if (inertia_out) *inertia_out = h[0].inertia;
     return pcr_d2h_staged(ctx, labels_out, d_labels.p, sizeof(int32_t) * n);
-}
-
-int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows, int64_t m, double* xyz_out) {
-    if (!ctx || !cloud || !rows || !xyz_out || m < 0 || m > KM_MAX_ROWS) return PCR_E_INVALID;
-    if (m == 0) return PCR_OK;
-    const int64_t n = cloud->n;
-    std::vector<std::pair<long long, long long>> order((size_t)m);
-    for (int64_t i = 0; i < m; ++i) {
-        if (rows[i] < 0 || rows[i] >= n) return PCR_E_INVALID;
-        order[(size_t)i] = {(long long)rows[i], (long long)i};
-    }
-    std::sort(order.begin(), order.end());
-    std::vector<long long> packed(2 * (size_t)m);
-    for (int64_t i = 0; i < m; ++i) { packed[(size_t)i] = order[(size_t)i].first; packed[(size_t)(m + i)] = order[(size_t)i].second; }
-    hipSetDevice(ctx->device);
-    pcr_dev_block d_rows(ctx), d_out(ctx);
-    int rc;
-    if ((rc = d_rows.alloc(sizeof(long long) * 2 * m)) || (rc = d_out.alloc(sizeof(double) * 3 * m))) return rc;
-    PCR_HIP(ctx, hipMemcpyAsync(d_rows.p, packed.data(), sizeof(long long) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
-    PCR_HIP(ctx, hipMemsetAsync(d_out.p, 0xff, sizeof(double) * 3 * m, ctx->stream));   // NaN: a row no record carries as its id
-    hipLaunchKernelGGL(cloud_gather_rows_kernel, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const pcr_pt*)cloud->d, (long long)n,
-                       d_rows.as<long long>(), d_rows.as<long long>() + m, (int)m, d_out.as<double>());
-    PCR_HIP(ctx, hipGetLastError());
-    return pcr_d2h_small(ctx, xyz_out, d_out.p, sizeof(double) * 3 * m);
 }
 
 }  // extern "C"

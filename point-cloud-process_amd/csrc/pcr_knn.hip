@@ -720,9 +720,9 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
         //   2. ONE QUERY PER WAVE for what it leaves: all 64 lanes scan the query's own box -- its cells and a ring, then the ball its
         //      k-th distance so far defines, or rings of 4, 16, 64 ... cells while it lacks k points (knn_tile_kernel);
         //   3. the lane-per-query scan at every level and the wave-per-query descent for what is left (clamped coordinates).
-        unsigned int* d_cnt_a = ctx->d_counters + 125;   // queries stage 2 left
-        unsigned int* d_cnt_b = ctx->d_counters + 126;   // queries the full block scan left (-> descent)
-        unsigned int* d_cnt_d = ctx->d_counters + 127;   // queries stage 1 left
+        unsigned int* d_cnt_a = pcr_counter(ctx, PCR_CW_KNN_LEFT);      // queries stage 2 left
+        unsigned int* d_cnt_b = pcr_counter(ctx, PCR_CW_KNN_LEFT, 1);   // queries the full block scan left (-> descent)
+        unsigned int* d_cnt_d = pcr_counter(ctx, PCR_CW_KNN_LEFT, 2);   // queries stage 1 left
         pcr_dev_block b_redo2(ctx), b_redo4(ctx), b_kth(ctx);
         if ((rc = b_redo.alloc(sizeof(int) * q)) || (rc = b_redo2.alloc(sizeof(int) * q)) || (rc = b_redo4.alloc(sizeof(int) * q)) || (rc = b_kth.alloc(sizeof(double) * q))) return rc;
         double* d_kth = b_kth.as<double>();   // stage 1 hands the k-th distance it found to stage 2 as the first ball

@@ -239,7 +239,7 @@ int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out
     if ((rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&d_ev))) return rc;
     if ((rc = pcr_dev_alloc(ctx, sizeof(int) * (size_t)k * n, (void**)&d_nbr))) return rc;
     if ((rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&d_redo))) return rc;
-    unsigned int* d_count = ctx->d_counters + 112;
+    unsigned int* d_count = pcr_counter(ctx, PCR_CW_NORMALS_REDO);
     PCR_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
     const unsigned grid = (unsigned)((n + 255) / 256);
 #define PCR_NK(K) case K: hipLaunchKernelGGL(normals_kernel<K>, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, d_nrm, d_ev, d_nbr, d_redo, d_count); break;

@@ -15,12 +15,13 @@
 #include "pcr_internal.h"
 #include "pcr_linalg.h"
 #include "pcr_icp_step.h"
-#include "pcr_grid_dev.h"
+#include "pcr_stream_fit.h"   // pcr_events_ms
+#include "pcr_wave.h"
+#include "pcr_grid_dev.h"     // xform_apply
 
 namespace {
 
 constexpr int P2P_NSUM = 29;         // A upper triangle (21), b (6), K, sum d^2
-constexpr int P2P_TICKET_WORD = 72;  // word of ctx->d_counters (zero at context creation, re-armed by the last block)
 
 // Loop state on the device.  The head (everything before the logs) is what the host reads every iteration.
 struct __attribute__((aligned(16))) p2p_state {
@@ -79,7 +80,7 @@ __global__ void __launch_bounds__(256)
 point2plane_accumulate_kernel(const pcr_pt* __restrict__ q, long long nq, const int* __restrict__ nn_idx, const pcr_pt* __restrict__ tgt,
                               const double* __restrict__ nrm, const int* __restrict__ row_pos, p2p_T T_arg, double* __restrict__ partials,
                               unsigned int* __restrict__ ticket, double* __restrict__ out, p2p_state* __restrict__ st, p2p_loop_args la) {
-    __shared__ double s_part[4][P2P_NSUM];
+    __shared__ double s_part[4][P2P_NSUM], s_red[8][P2P_NSUM], s_tot[P2P_NSUM];
     if (st && st->stop) return;
     pcr_xform x;
 #pragma unroll
@@ -145,46 +146,10 @@ point2plane_accumulate_kernel(const pcr_pt* __restrict__ q, long long nq, const 
 #pragma unroll
         for (int k = 0; k < P2P_NSUM; ++k) s_part[wave][k] = m[k];
     }
-    __syncthreads();
-    if (threadIdx.x < P2P_NSUM) {
-        const double v = (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]);
-        partials[(long long)blockIdx.x * P2P_NSUM + threadIdx.x] = v;
-    }
-    // the block that arrives last adds the slabs in block order: the hand-off of grid_accumulate_kernel (drained stores -> barrier ->
-    // agent-scope release -> ticket; last arriver: agent-scope acquire -> barrier -> plain loads)
-    __shared__ unsigned int s_last;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (t == gridDim.x - 1) ? 1u : 0u;
-        if (s_last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            *ticket = 0;  // ready for the next launch (stream-ordered)
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __shared__ double s_red[8][32];
-    const int k = threadIdx.x & 31, slice = threadIdx.x >> 5;  // 8 strided slices of the slabs, then a fixed tree
-    double v = 0.0;
-    if (k < P2P_NSUM)
-        for (int b = slice; b < (int)gridDim.x; b += 8) v += partials[(long long)b * P2P_NSUM + k];
-    s_red[slice][k] = v;
-    __syncthreads();
-    __shared__ double s_m[32];
-    if (slice == 0 && k < P2P_NSUM) {
-        const double tot = ((s_red[0][k] + s_red[1][k]) + (s_red[2][k] + s_red[3][k])) + ((s_red[4][k] + s_red[5][k]) + (s_red[6][k] + s_red[7][k]));
-        if (out) out[k] = tot;
-        s_m[k] = tot;
-    }
-    if (st) {
-        __syncthreads();
-        if (threadIdx.x == 0) p2p_finish_pass(st, s_m, nq, la);
-    }
+    // one slab per block; the block that arrives last adds the slabs in a fixed order
+    if (!block_slab_sums<P2P_NSUM>(s_part, P2P_NSUM, partials, ticket, s_red, s_tot, [](double a, double b, int) { return a + b; })) return;
+    if (out && threadIdx.x < P2P_NSUM) out[threadIdx.x] = s_tot[threadIdx.x];
+    if (st && threadIdx.x == 0) p2p_finish_pass(st, s_tot, nq, la);
 }
 
 // loop state before the first pass: zero, T = T0
@@ -237,7 +202,7 @@ int p2p_pass(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const doub
     const bool grid = index->kind == PCR_INDEX_GRID;
     hipLaunchKernelGGL(point2plane_accumulate_kernel, dim3(sc->grid), dim3(256), 0, ctx->stream, (const pcr_pt*)source->d, (long long)source->n,
                        (const int*)sc->nn_idx.p, (const pcr_pt*)(grid ? index->sorted : index->plain), (const double*)index->normals,
-                       (const int*)(grid ? index->row_pos : nullptr), Ta, ctx->d_partials, ctx->d_counters + P2P_TICKET_WORD, d_out, d_st, la);
+                       (const int*)(grid ? index->row_pos : nullptr), Ta, ctx->d_partials, pcr_counter(ctx, PCR_CW_P2P_TICKET), d_out, d_st, la);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
@@ -352,10 +317,7 @@ int pcr_icp_point2plane(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* 
     }
     delete full;
     if (rc) return rc;
-    PCR_HIP(ctx, pcr_event_sync(ctx->ev1));
-    float ms = 0;
-    hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    res->device_ms = ms;
+    if ((rc = pcr_events_ms(ctx, &res->device_ms))) return rc;
     return res->status;
 }
 

@@ -421,11 +421,11 @@ static int voxel_groups(pcr_ctx* ctx, const pcr_cloud* c, double leaf, int end_b
     if (e == hipSuccess) rc = pcr_dev_alloc(ctx, temp_bytes, &d_temp);
     if (e == hipSuccess && rc == PCR_OK) e = pcr_sort_pairs(d_temp, temp_bytes, d_keys, d_keys2, d_vals, d_perm, (size_t)n, (unsigned int)end_bit, ctx->stream);
     if (e == hipSuccess && rc == PCR_OK) {
-        w->big_count = ctx->d_counters + 49;
+        w->big_count = pcr_counter(ctx, PCR_CW_VOXEL, 1);
         hipLaunchKernelGGL(voxel_gather_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (const unsigned int*)d_perm, n, w->xyz, w->big_count);
         // group heads = positions whose key differs from the previous one: one fused flag + scan + scatter (rocprim::select
         // over a counting iterator with a computed flag), instead of a flag kernel, a scan and a scatter
-        w->n_groups = ctx->d_counters + 48;
+        w->n_groups = pcr_counter(ctx, PCR_CW_VOXEL);
         const head_flag<K> flag_op{d_keys2};
         auto positions = rocprim::counting_iterator<unsigned int>(0u);
         auto flags = rocprim::make_transform_iterator(positions, flag_op);
@@ -589,8 +589,8 @@ int pcr_voxel_downsample_scans(pcr_ctx* ctx, const float* d_xyz, int64_t n_pts, 
     PCR_HIP(ctx, pcr_sort_pairs(nullptr, temp_bytes, d_keys, d_keys2, b_vals.as<unsigned int>(), b_perm.as<unsigned int>(), (size_t)n, (unsigned int)end_bit, ctx->stream));
     if ((rc = b_temp.alloc(temp_bytes))) return rc;
     PCR_HIP(ctx, pcr_sort_pairs(b_temp.p, temp_bytes, d_keys, d_keys2, b_vals.as<unsigned int>(), b_perm.as<unsigned int>(), (size_t)n, (unsigned int)end_bit, ctx->stream));
-    unsigned int* const big_count = ctx->d_counters + 49;
-    unsigned int* const n_groups = ctx->d_counters + 48;
+    unsigned int* const big_count = pcr_counter(ctx, PCR_CW_VOXEL, 1);
+    unsigned int* const n_groups = pcr_counter(ctx, PCR_CW_VOXEL);
     hipLaunchKernelGGL(scans_gather_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, d_xyz, (const unsigned int*)b_perm.as<unsigned int>(), n, b_xyz.as<vox_xyz>(), big_count);
     const head_flag<unsigned long long> flag_op{d_keys2};
     auto positions = rocprim::counting_iterator<unsigned int>(0u);

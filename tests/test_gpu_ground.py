@@ -155,11 +155,18 @@ def test_quirks(pcp):
     check_against(pcp, pts, np.array([repeated, collinear, [4, 4, 4]]), tau=tau)
 
 
-@pytest.mark.parametrize("n", [777, 5000])
+@pytest.mark.parametrize("n", [777, 1025, 5000])
 def test_reordered_cloud(pcp, ctx, n):
-    """A cloud laid out for queries against a grid index (records in Morton order, id = caller row) gives what the fresh upload gives."""
+    """A cloud laid out for queries against a grid index (records in Morton order, id = caller row) gives what the fresh upload gives.
+    n = 1025 (just over one scoring tile): four hypotheses, one with a repeated row (NaN plane, count 0) and one that shares a row
+    with another, so the sampled points reach the planes through the shared row gather with fewer distinct rows than samples."""
     pts = scene(n)
     samples = reference_draws(n)
+    if n == 1025:
+        samples = np.random.default_rng(1025).choice(n, size=(4, 3), replace=False)
+        samples[1, 1] = samples[1, 0]   # a repeated row
+        samples[2, 0] = samples[0, 2]   # a row of hypothesis 0 again in hypothesis 2
+        assert restate(pts, samples)["counts"][1] == 0 and len(np.unique(samples)) == 10
     index = pcp.TargetIndex(scene(20000), kind="grid", ctx=ctx)
     dc = pcp.DeviceCloud.upload(pts, ctx)
     dc.prepare(index)
