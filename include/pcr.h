@@ -67,6 +67,9 @@ PCR_API int pcr_cloud_upload_f32(pcr_ctx* ctx, const float* xyz, int64_t n, int6
 PCR_API int pcr_cloud_upload_f64(pcr_ctx* ctx, const double* xyz, int64_t n, int64_t stride_doubles, pcr_cloud** out);
 PCR_API int pcr_cloud_download_f64(pcr_ctx* ctx, const pcr_cloud* cloud, double* xyz_out /* n*3 */);
 PCR_API int64_t pcr_cloud_size(const pcr_cloud* cloud);
+/* diagnostic: 1 when the cloud's records have been laid out along an index's curve (it was the query cloud of a grid search),
+ * 0 when they are still in the caller's row order.  Results never depend on it; searches choose their path by it. */
+PCR_API int pcr_cloud_reordered(const pcr_cloud* cloud);
 PCR_API int pcr_cloud_free(pcr_ctx* ctx, pcr_cloud* cloud);
 /* Optional: lay the cloud out for queries against `index` now (Morton order of its records; row
  * ids are kept, downloads are unaffected).  pcr_nn1 / pcr_icp do this themselves on first use. */
@@ -383,6 +386,18 @@ PCR_API int pcr_global_default_params(double voxel_size, pcr_global_params* p);
 PCR_API int pcr_register_pairs(pcr_ctx* const* ctxs, int n_ctx, const pcr_cloud_ref* clouds, int64_t n_clouds, const pcr_pair_ref* pairs,
                                int64_t n_pairs, const pcr_global_params* global, const pcr_icp_params* icp, pcr_icp_result* results,
                                int32_t* status_out, double* T_init_out);
+/* DIAGNOSTIC entry point -- a seam for tests, not part of the pair loop: the fused initialisation's matching step alone, on
+ * descriptors the caller brings.  descriptors (ng,33) row-major hold n_sets descriptor sets one behind the other, set s = rows
+ * [set_first[s], set_first[s + 1]) (set_first[0] = 0, every set non-empty); pair_sets (n_pairs,2) = (source set, target set).
+ * The sets are turned into the matrix-core operands and matched exactly as the scans of a share are (one launch for all pairs;
+ * how the targets are split depends on the number of pairs and the device).  Outputs, pair behind pair in the order given:
+ * ij_out / dab_out (na per pair): nearest target row of every source row and its squared distance; ji_out / dba_out (nb per
+ * pair): the other way (written only with mutual_filter); corr_out (na,2 per pair) of which the first m_out[pair] rows are the
+ * correspondence set pcr_global_registration would sample from.  A set above 4096 rows: PCR_E_UNSUPPORTED (the fused path
+ * declines such scans); more than 2048 sets, an empty set, a set index out of range: PCR_E_INVALID.                      */
+PCR_API int pcr_match_pairs_fused(pcr_ctx* ctx, const double* descriptors, const int64_t* set_first, int64_t n_sets, const int32_t* pair_sets,
+                                  int64_t n_pairs, int mutual_filter, int32_t* ij_out, double* dab_out, int32_t* ji_out, double* dba_out,
+                                  int32_t* corr_out, int32_t* m_out);
 
 /* ------------------------------------------------------------------ DBSCAN
  * DBSCAN.fit (Cluster_dbscan/dbscan.py:10-36), a consumer of the radius query:

@@ -100,47 +100,83 @@ def pair_features(p1, n1, p2, n2):
     return np.array([f0, f1, f2])
 
 
-def _bin(x):
-    return int(min(max(np.floor(x), 0), 10))
+def _pair_features_many(p1, n1, p2, n2):
+    """pair_features for (P,3) arrays of pairs at once: the same operations in the same order, element by element."""
+    d = p2 - p1
+    ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    live = ln != 0.0
+    lns = np.where(live, ln, 1.0)
+    a1 = ((n1[:, 0] * d[:, 0] + n1[:, 1] * d[:, 1]) + n1[:, 2] * d[:, 2]) / lns
+    a2 = ((n2[:, 0] * d[:, 0] + n2[:, 1] * d[:, 1]) + n2[:, 2] * d[:, 2]) / lns
+    swap = np.abs(a1) < np.abs(a2)
+    u = np.where(swap[:, None], n2, n1)
+    w2 = np.where(swap[:, None], n1, n2)
+    d = np.where(swap[:, None], -d, d)
+    f2 = np.where(swap, -a2, a1)
+    v = np.stack([d[:, 1] * u[:, 2] - d[:, 2] * u[:, 1], d[:, 2] * u[:, 0] - d[:, 0] * u[:, 2], d[:, 0] * u[:, 1] - d[:, 1] * u[:, 0]], axis=1)
+    vn = np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+    live &= vn != 0.0
+    v = v / np.where(live, vn, 1.0)[:, None]
+    w = np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1], u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2], u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], axis=1)
+    f1 = (v[:, 0] * w2[:, 0] + v[:, 1] * w2[:, 1]) + v[:, 2] * w2[:, 2]
+    f0 = np.arctan2((w[:, 0] * w2[:, 0] + w[:, 1] * w2[:, 1]) + w[:, 2] * w2[:, 2], (u[:, 0] * w2[:, 0] + u[:, 1] * w2[:, 1]) + u[:, 2] * w2[:, 2])
+    return np.where(live[:, None], np.stack([f0, f1, f2], axis=1), 0.0)
 
 
-def spfh(points, normals, nbrs):
+def spfh(points, normals, nbrs, margins=False):
+    """SPFH rows (N,33): every pair (point, neighbour behind the first entry of its list) adds 100 / (k - 1) to one bin of each block,
+    one addition after the other.  ``margins=True`` also returns, per point, the smallest distance of any of its pairs' three bin
+    coordinates (11 * x, before the floor) from an integer: a pair that close to a bin edge may land on either side of it under
+    another libm or another rounding (inf for a point without pairs)."""
     p = np.asarray(points, dtype=np.float64)
-    out = np.zeros((len(p), 33))
-    for i, (idx, _) in enumerate(nbrs):
-        if len(idx) <= 1:
-            continue
-        incr = 100.0 / (len(idx) - 1)
-        for k in idx[1:]:
-            f = pair_features(p[i], normals[i], p[k], normals[k])
-            out[i, _bin(11 * (f[0] + np.pi) / (2.0 * np.pi))] += incr
-            out[i, 11 + _bin(11 * (f[1] + 1.0) * 0.5)] += incr
-            out[i, 22 + _bin(11 * (f[2] + 1.0) * 0.5)] += incr
-    return out
+    nrm = np.asarray(normals, dtype=np.float64)
+    n = len(p)
+    lens = np.array([len(idx) for idx, _ in nbrs])
+    I = np.repeat(np.arange(n), np.maximum(lens - 1, 0))
+    K = np.concatenate([np.asarray(idx[1:], dtype=np.int64) for idx, _ in nbrs] + [np.zeros(0, dtype=np.int64)])
+    f = _pair_features_many(p[I], nrm[I], p[K], nrm[K])
+    x = np.stack([11 * (f[:, 0] + np.pi) / (2.0 * np.pi), 11 * (f[:, 1] + 1.0) * 0.5, 11 * (f[:, 2] + 1.0) * 0.5], axis=1)
+    bins = np.minimum(np.maximum(np.floor(x), 0), 10).astype(np.int64) + np.array([0, 11, 22])
+    hist = np.zeros((n, 33), dtype=np.int64)
+    np.add.at(hist, (np.repeat(I, 3), bins.reshape(-1)), 1)
+    incr = 100.0 / np.maximum(lens - 1, 1)
+    out = np.zeros((n, 33))
+    for c in range(1, int(hist.max(initial=0)) + 1):       # hist[i, b] additions of incr[i], one after the other
+        out = np.where(hist >= c, out + incr[:, None], out)
+    if not margins:
+        return out
+    margin = np.full(n, np.inf)
+    np.minimum.at(margin, I, np.abs(x - np.round(x)).min(axis=1))
+    return out, margin
 
 
-def fpfh(points, normals, radius, max_nn=100, nbrs=None):
+def fpfh(points, normals, radius, max_nn=100, nbrs=None, margins=False):
     """main.py:44-46 -> (N,33): SPFH of the point + 1/d^2-weighted SPFH of its neighbours, each of the three
-    11-bin blocks of the weighted part renormalised to 100."""
+    11-bin blocks of the weighted part renormalised to 100.  ``margins=True`` -> (rows, margin): per row the smallest bin-edge
+    margin (see spfh) over the row itself and every row of its neighbour list, i.e. over every pair its value depends on."""
     p = np.asarray(points, dtype=np.float64)
     nbrs = nbrs or hybrid_neighbours(p, radius, max_nn)
-    s = spfh(p, normals, nbrs)
-    out = np.zeros_like(s)
+    s, own = spfh(p, normals, nbrs, margins=True)
+    n = len(p)
+    lens = np.array([len(idx) for idx, _ in nbrs])
+    width = int(lens.max(initial=1))
+    ids = np.zeros((n, width), dtype=np.int64)
+    d2s = np.zeros((n, width))                              # (0 = no such neighbour: skipped like a neighbour at distance 0)
     for i, (idx, d2) in enumerate(nbrs):
-        if len(idx) <= 1:
-            continue
-        acc = np.zeros(33)
-        tot = np.zeros(3)
-        for k, dd in zip(idx[1:], d2[1:]):
-            if dd == 0.0:
-                continue
-            val = s[k] / dd
-            acc += val
-            for j in range(33):
-                tot[j // 11] += val[j]
-        scale = np.where(tot != 0.0, 100.0 / np.where(tot != 0.0, tot, 1.0), 0.0)
-        out[i] = acc * np.repeat(scale, 11) + s[i]
-    return out
+        ids[i, :len(idx)], d2s[i, :len(idx)] = idx, d2
+    acc = np.zeros((n, 33))
+    tot = np.zeros((n, 3))
+    for r in range(1, width):                               # neighbour by neighbour, in list order, for all points at once
+        use = d2s[:, r] != 0.0
+        val = s[ids[:, r]] / np.where(use, d2s[:, r], 1.0)[:, None]
+        acc = np.where(use[:, None], acc + val, acc)
+        for j in range(11):                                 # the three totals: bin after bin of their block
+            tot = np.where(use[:, None], tot + val[:, [j, 11 + j, 22 + j]], tot)
+    scale = np.where(tot != 0.0, 100.0 / np.where(tot != 0.0, tot, 1.0), 0.0)
+    out = np.where((lens > 1)[:, None], acc * np.repeat(scale, 11, axis=1) + s, 0.0)
+    if not margins:
+        return out
+    return out, np.array([min(own[i], own[idx].min()) if len(idx) else own[i] for i, (idx, _) in enumerate(nbrs)])
 
 
 def feature_match(A, B):
@@ -175,7 +211,8 @@ def kabsch(A, B):
 
 def ransac(src, tgt, corr, max_iteration=100000, confidence=0.999, max_distance=3.0, edge_similarity=0.9, check_distance=True, seed=0):
     """main.py:73-83 / icp_template.py:88-110: sequential loop with running best and confidence-based exit.
-    Returns dict(T, best_iteration, iterations, n_valid, corr_fitness, corr_rmse, inliers)."""
+    Returns dict(T, best_iteration, iterations, n_valid, corr_fitness, corr_rmse, inliers, k_values); k_values: every k the
+    confidence rule computed (before its ceil), in order -- a caller can check that none sits at an integer's edge."""
     src = np.asarray(src, dtype=np.float64)
     tgt = np.asarray(tgt, dtype=np.float64)
     corr = np.asarray(corr)
@@ -185,6 +222,7 @@ def ransac(src, tgt, corr, max_iteration=100000, confidence=0.999, max_distance=
     exit_itr = max_iteration
     n_valid = 0
     itr = 0
+    k_values = []
     while itr < exit_itr:
         c = [mix64(seed ^ mix64(itr * 3 + j)) % m for j in range(3)]
         s, t = S[c], Tg[c]
@@ -213,8 +251,9 @@ def ransac(src, tgt, corr, max_iteration=100000, confidence=0.999, max_distance=
                 best.update(T=T, best_iteration=itr, corr_fitness=fit, corr_rmse=rmse, inliers=good)
                 x = 1.0 - fit ** 3
                 k = 0.0 if x <= 0 else np.log(1.0 - confidence) / np.log(x)
+                k_values.append(float(k))
                 if k < max_iteration:
                     exit_itr = min(exit_itr, int(np.ceil(k)))
         itr += 1
-    best.update(iterations=min(itr, exit_itr), n_valid=n_valid)
+    best.update(iterations=min(itr, exit_itr), n_valid=n_valid, k_values=k_values)
     return best

@@ -242,6 +242,7 @@ SIGNATURES = {
     "pcr_cloud_upload_f64": (C.c_int, [_vp, _dp, C.c_int64, C.c_int64, C.POINTER(_vp)]),
     "pcr_cloud_download_f64": (C.c_int, [_vp, _vp, _dp]),
     "pcr_cloud_size": (C.c_int64, [_vp]),
+    "pcr_cloud_reordered": (C.c_int, [_vp]),
     "pcr_cloud_free": (C.c_int, [_vp, _vp]),
     "pcr_cloud_transform": (C.c_int, [_vp, _vp, _dp]),
     "pcr_cloud_prepare": (C.c_int, [_vp, _vp, _vp]),
@@ -266,6 +267,7 @@ SIGNATURES = {
     "pcr_global_default_params": (C.c_int, [C.c_double, C.POINTER(GlobalParams)]),
     "pcr_register_pairs": (C.c_int, [C.POINTER(_vp), C.c_int, C.POINTER(CloudRef), C.c_int64, C.POINTER(PairRef), C.c_int64, C.POINTER(GlobalParams),
                                      C.POINTER(IcpParams), C.POINTER(IcpResult), _ip, _dp]),
+    "pcr_match_pairs_fused": (C.c_int, [_vp, _dp, _lp, C.c_int64, _ip, C.c_int64, C.c_int, _ip, _dp, _ip, _dp, _ip, _ip]),
     "pcr_icp_moments": (C.c_int, [_vp, _vp, _vp, _dp, C.c_double, _dp, _dp, _dp]),
     "pcr_procrustes": (C.c_int, [_dp, _dp, C.c_int64, _dp, _dp, _dp]),
     "pcr_homo2tq": (C.c_int, [_dp, _dp]),

@@ -725,6 +725,7 @@ int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
 }
 
 int64_t pcr_cloud_size(const pcr_cloud* c) { return c ? c->n : 0; }
+int pcr_cloud_reordered(const pcr_cloud* c) { return c && c->morton_sorted ? 1 : 0; }
 
 int pcr_cloud_free(pcr_ctx* ctx, pcr_cloud* c) {
     if (!c) return PCR_OK;

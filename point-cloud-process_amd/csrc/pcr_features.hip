@@ -302,7 +302,8 @@ __device__ static bool spfh_body(const pcr_grid_view& gv, const pcr_pt& p, doubl
     if (threadIdx.x < 33) hist[threadIdx.x] = 0;
     const int cnt = gather_hybrid<CAP>(gv, p.x, p.y, p.z, r2, max_nn, L);  // ends with a barrier
     if (cnt == -2) return false;
-    if (cnt < 0) { if (threadIdx.x == 0) atomicAdd(fail, 1); return true; }
+    // (an empty list: the FPFH launch behind this one reads every point's count -- and walks that many entries -- before the host sees the fail word)
+    if (cnt < 0) { if (threadIdx.x == 0) { atomicAdd(fail, 1); nb_cnt[p.id] = 0; } return true; }
     const double p1[3] = {p.x, p.y, p.z};
     const double n1[3] = {normals[3 * p.id], normals[3 * p.id + 1], normals[3 * p.id + 2]};
     for (int k = threadIdx.x; k < cnt; k += 64) {

@@ -237,10 +237,30 @@ void pack_chunk(init_share& S, size_t k) {
                  [&](int64_t q) { pack_scan(S.clouds[P.who[(size_t)q]], h_xyz + 3 * (size_t)P.ds[(size_t)q].first_pt, &P.ds[(size_t)q]); });
 }
 
+// the matching operands of a chunk's descriptors (c.fpfh, c.scan_first, c.first, c.n_scans, c.ng are set): tile table, operands, norms.
+// Reads the fail word, which synchronises: the scratch taken here -- and the caller's -- is free when this returns.
+int chunk_match_operands(pcr_ctx* ctx, scan_chunk& c) {
+    const size_t ng = (size_t)c.ng, ns1 = (size_t)c.n_scans + 1;
+    int rc;
+    c.tile_first.assign(ns1, 0u);
+    for (int k = 0; k < c.n_scans; ++k) c.tile_first[(size_t)k + 1] = c.tile_first[(size_t)k] + (c.first[(size_t)k + 1] - c.first[(size_t)k] + 15u) / 16u;
+    const size_t tiles = c.tile_first[(size_t)c.n_scans], op_bytes = 8 * 64 * (size_t)FM_STEPS * (tiles ? tiles : 1);
+    pcr_dev_block b_tf(ctx), b_dup(ctx);
+    if ((rc = b_dup.alloc(ng ? ng : 1)) || (rc = c.op_t.alloc(op_bytes)) || (rc = c.op_q.alloc(op_bytes)) || (rc = c.norm2.alloc(8 * (ng ? ng : 1))) ||
+        (rc = c.max_norm2.alloc(8 * ns1)) || (rc = c.min_row.alloc(4 * ns1)) || (rc = b_tf.alloc(4 * ns1)))
+        return rc;
+    if (hipMemcpyAsync(b_tf.p, c.tile_first.data(), 4 * ns1, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PCR_E_HIP;
+    if (hipMemsetAsync(c.max_norm2.p, 0, 8 * ns1, ctx->stream) != hipSuccess) return PCR_E_HIP;
+    pcr_match_operands(ctx, c.fpfh.as<double>(), c.scan_first.as<unsigned int>(), c.n_scans, tiles, b_tf.as<unsigned int>(), b_dup.as<unsigned char>(), c.op_t.as<double>(),
+                       c.op_q.as<double>(), c.norm2.as<double>(), c.max_norm2.as<unsigned long long>(), c.min_row.as<unsigned int>());
+    if (hipGetLastError() != hipSuccess) return PCR_E_HIP;
+    return pcr_read_fail(ctx);   // (synchronises: the tile table and the duplicate marks are done with)
+}
+
 // normals, SPFH, FPFH and the matching operands of a down-sampled chunk.  The per-point scratch lives to the end: read_fail synchronises.
 int describe_chunk(init_share& S, scan_chunk& c) {
     pcr_ctx* const ctx = S.ctx;
-    const size_t ng = (size_t)c.ng, nn = (size_t)S.g->fpfh_max_nn, ns1 = (size_t)c.n_scans + 1;
+    const size_t ng = (size_t)c.ng, nn = (size_t)S.g->fpfh_max_nn;
     pcr_dev_block b_nrm(ctx), b_spfh(ctx), b_id(ctx), b_d2(ctx), b_cnt(ctx);
     int rc;
     if ((rc = c.fpfh.alloc(sizeof(double) * 33 * ng)) || (rc = b_nrm.alloc(sizeof(double) * 3 * ng)) || (rc = b_spfh.alloc(sizeof(double) * 33 * ng)) ||
@@ -251,19 +271,7 @@ int describe_chunk(init_share& S, scan_chunk& c) {
     const scans_view V{c.down.as<pcr_pt>(), c.vsid.as<unsigned int>(), c.scan_first.as<unsigned int>()};
     const scans_scratch W{b_nrm.as<double>(), b_spfh.as<double>(), b_id.as<unsigned int>(), b_d2.as<double>(), b_cnt.as<int>(), b_redo.as<unsigned int>(), b_cov.as<double>()};
     if ((rc = pcr_scans_features(ctx, V, ng, S.g, W, c.fpfh.as<double>()))) return rc;
-    c.tile_first.assign(ns1, 0u);
-    for (int k = 0; k < c.n_scans; ++k) c.tile_first[(size_t)k + 1] = c.tile_first[(size_t)k] + (c.first[(size_t)k + 1] - c.first[(size_t)k] + 15u) / 16u;
-    const size_t tiles = c.tile_first[(size_t)c.n_scans], op_bytes = 8 * 64 * (size_t)FM_STEPS * (tiles ? tiles : 1);
-    pcr_dev_block b_tf(ctx), b_dup(ctx);
-    if ((rc = b_dup.alloc(ng ? ng : 1)) || (rc = c.op_t.alloc(op_bytes)) || (rc = c.op_q.alloc(op_bytes)) || (rc = c.norm2.alloc(8 * (ng ? ng : 1))) ||
-        (rc = c.max_norm2.alloc(8 * ns1)) || (rc = c.min_row.alloc(4 * ns1)) || (rc = b_tf.alloc(4 * ns1)))
-        return rc;
-    if (hipMemcpyAsync(b_tf.p, c.tile_first.data(), 4 * ns1, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PCR_E_HIP;
-    if (hipMemsetAsync(c.max_norm2.p, 0, 8 * ns1, ctx->stream) != hipSuccess) return PCR_E_HIP;
-    pcr_match_operands(ctx, c.fpfh.as<double>(), V.scan_first, c.n_scans, tiles, b_tf.as<unsigned int>(), b_dup.as<unsigned char>(), c.op_t.as<double>(), c.op_q.as<double>(),
-                       c.norm2.as<double>(), c.max_norm2.as<unsigned long long>(), c.min_row.as<unsigned int>());
-    if (hipGetLastError() != hipSuccess) return PCR_E_HIP;
-    rc = pcr_read_fail(ctx);   // (synchronises: the chunk's scratch -- and the tile table -- and the pinned block are free for the next chunk)
+    rc = chunk_match_operands(ctx, c);   // (synchronises: the chunk's scratch and the pinned block are free for the next chunk)
     S.lap("normals + SPFH + FPFH");
     return rc;
 }
@@ -388,22 +396,34 @@ int ransac_jobs(init_share& S, const job_table& tab, const init_job* d_jobs, con
     return PCR_OK;
 }
 
+// the device side of a job table: the pool its arrays are cut from, the jobs, the list of running ones, their loop states
+struct job_pool {
+    pcr_dev_block b_i, b_d, b_jobs, b_act, b_st;
+    explicit job_pool(pcr_ctx* c) : b_i(c), b_d(c), b_jobs(c), b_act(c), b_st(c) {}
+};
+// matching both ways, correspondence set and initial loop state of every job of the table (enqueued; tab.jobs gets the device addresses)
+int match_jobs(pcr_ctx* ctx, job_table& tab, job_pool& P, int mutual, int max_iteration) {
+    const int nj = (int)tab.jobs.size();
+    int rc;
+    if ((rc = P.b_i.alloc(4 * tab.n_i)) || (rc = P.b_d.alloc(8 * tab.n_d)) || (rc = P.b_jobs.alloc(sizeof(init_job) * nj)) || (rc = P.b_act.alloc(4 * (size_t)nj)) ||
+        (rc = P.b_st.alloc(sizeof(ransac_state) * (size_t)nj)))
+        return rc;
+    place_jobs(tab.jobs, P.b_i.as<int>(), P.b_d.as<double>(), P.b_st.as<ransac_state>());
+    if (hipMemcpyAsync(P.b_jobs.p, tab.jobs.data(), sizeof(init_job) * nj, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PCR_E_HIP;
+    pcr_match_jobs(ctx, P.b_jobs.as<init_job>(), nj, tab.max_n, mutual, max_iteration);
+    return PCR_OK;
+}
+
 // matching, correspondence sets and RANSAC of up to PAIR_CHUNK pairs side by side
 int register_pairs(init_share& S, const pcr_pair_ref* pairs, const int64_t* todo, int64_t n_todo, double* T_init) {
     pcr_ctx* const ctx = S.ctx;
     job_table tab = build_jobs(S, pairs, todo, n_todo);
-    const int nj = (int)tab.jobs.size();
-    if (nj == 0) return PCR_OK;
-    pcr_dev_block b_i(ctx), b_d(ctx), b_jobs(ctx), b_act(ctx), b_st(ctx);
+    if (tab.jobs.empty()) return PCR_OK;
+    job_pool P(ctx);
     int rc;
-    if ((rc = b_i.alloc(4 * tab.n_i)) || (rc = b_d.alloc(8 * tab.n_d)) || (rc = b_jobs.alloc(sizeof(init_job) * nj)) || (rc = b_act.alloc(4 * (size_t)nj)) ||
-        (rc = b_st.alloc(sizeof(ransac_state) * (size_t)nj)))
-        return rc;
-    place_jobs(tab.jobs, b_i.as<int>(), b_d.as<double>(), b_st.as<ransac_state>());
-    if (hipMemcpyAsync(b_jobs.p, tab.jobs.data(), sizeof(init_job) * nj, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return PCR_E_HIP;
-    pcr_match_jobs(ctx, b_jobs.as<init_job>(), nj, tab.max_n, S.g->mutual_filter ? 1 : 0, S.g->ransac.max_iteration);
+    if ((rc = match_jobs(ctx, tab, P, S.g->mutual_filter ? 1 : 0, S.g->ransac.max_iteration))) return rc;
     S.lap("matching + correspondences");
-    return ransac_jobs(S, tab, b_jobs.as<init_job>(), b_st.as<ransac_state>(), b_act.as<int>(), T_init);
+    return ransac_jobs(S, tab, P.b_jobs.as<init_job>(), P.b_st.as<ransac_state>(), P.b_act.as<int>(), T_init);
 }
 }  // namespace
 
@@ -425,4 +445,66 @@ int pcr_global_init_batch(pcr_ctx* ctx, const pcr_cloud_ref* clouds, int64_t n_c
     pcr_sync(ctx->stream);
     while (!S.chunks.empty()) S.chunks.pop_front();   // (first to last, behind the synchronisation)
     return rc;
+}
+
+// Diagnostic entry point (include/pcr.h): the fused path's matching alone, on descriptor sets the caller brings.  The sets become one
+// chunk whose "scans" they are -- operands by chunk_match_operands, jobs by build_jobs / match_jobs, as upload_chunk and register_pairs do.
+extern "C" int pcr_match_pairs_fused(pcr_ctx* ctx, const double* descriptors, const int64_t* set_first, int64_t n_sets, const int32_t* pair_sets, int64_t n_pairs,
+                                     int mutual_filter, int32_t* ij_out, double* dab_out, int32_t* ji_out, double* dba_out, int32_t* corr_out, int32_t* m_out) {
+    if (!ctx || !descriptors || !set_first || !pair_sets || !ij_out || !dab_out || !ji_out || !dba_out || !corr_out || !m_out) return PCR_E_INVALID;
+    if (n_sets < 1 || n_sets > CHUNK_SCANS || n_pairs < 1 || set_first[0] != 0) return PCR_E_INVALID;
+    for (int64_t s = 0; s < n_sets; ++s) {
+        if (set_first[s + 1] <= set_first[s]) return PCR_E_INVALID;
+        if (set_first[s + 1] - set_first[s] > HYBRID_BRUTE_MAX) return PCR_E_UNSUPPORTED;
+    }
+    for (int64_t p = 0; p < 2 * n_pairs; ++p)
+        if (pair_sets[p] < 0 || pair_sets[p] >= n_sets) return PCR_E_INVALID;
+    hipSetDevice(ctx->device);
+    pcr_global_params g;
+    pcr_global_default_params(2.0, &g);
+    init_share S{ctx, nullptr, &g, 1};
+    S.slot.resize((size_t)n_sets);
+    S.chunks.emplace_back(ctx);
+    scan_chunk& c = S.chunks.back();
+    c.ng = set_first[n_sets]; c.n_scans = (int)n_sets;
+    c.first.resize((size_t)n_sets + 1);
+    for (int64_t s = 0; s <= n_sets; ++s) c.first[(size_t)s] = (unsigned int)set_first[s];
+    for (int64_t s = 0; s < n_sets; ++s) S.slot[(size_t)s] = scan_slot{0, (int)s};
+    const size_t ng = (size_t)c.ng;
+    int rc;
+    // (no points behind these descriptors: the records a job's RANSAC would sample stay zero, and no RANSAC runs)
+    if ((rc = c.down.alloc(sizeof(pcr_pt) * ng)) || (rc = c.scan_first.alloc(4 * ((size_t)n_sets + 1))) || (rc = c.fpfh.alloc(sizeof(double) * 33 * ng))) return rc;
+    PCR_HIP(ctx, hipMemsetAsync(c.down.p, 0, sizeof(pcr_pt) * ng, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(c.scan_first.p, c.first.data(), 4 * ((size_t)n_sets + 1), hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(c.fpfh.p, descriptors, sizeof(double) * 33 * ng, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = chunk_match_operands(ctx, c))) return rc;
+    std::vector<pcr_pair_ref> pairs((size_t)n_pairs);
+    std::vector<int64_t> todo((size_t)n_pairs);
+    for (int64_t p = 0; p < n_pairs; ++p) { pairs[(size_t)p].src = pair_sets[2 * p]; pairs[(size_t)p].tgt = pair_sets[2 * p + 1]; pairs[(size_t)p].T0 = nullptr; todo[(size_t)p] = p; }
+    std::vector<size_t> at_a((size_t)n_pairs + 1, 0), at_b((size_t)n_pairs + 1, 0);   // where a pair's rows start in the outputs
+    for (int64_t p = 0; p < n_pairs; ++p) {
+        at_a[(size_t)p + 1] = at_a[(size_t)p] + (size_t)(set_first[pair_sets[2 * p] + 1] - set_first[pair_sets[2 * p]]);
+        at_b[(size_t)p + 1] = at_b[(size_t)p] + (size_t)(set_first[pair_sets[2 * p + 1] + 1] - set_first[pair_sets[2 * p + 1]]);
+    }
+    for (int64_t p0 = 0; p0 < n_pairs; p0 += PAIR_CHUNK) {
+        job_table tab = build_jobs(S, pairs.data(), todo.data() + p0, p0 + PAIR_CHUNK < n_pairs ? PAIR_CHUNK : n_pairs - p0);
+        job_pool P(ctx);
+        if ((rc = match_jobs(ctx, tab, P, mutual_filter ? 1 : 0, 1))) return rc;
+        PCR_HIP(ctx, hipGetLastError());
+        for (size_t j = 0; j < tab.jobs.size(); ++j) {   // (every set holds rows: a job per pair, in order)
+            const init_job& J = tab.jobs[j];
+            const size_t p = (size_t)tab.pair[j], a = at_a[p], b = at_b[p];
+            PCR_HIP(ctx, hipMemcpyAsync(ij_out + a, J.ij, 4 * (size_t)J.na, hipMemcpyDeviceToHost, ctx->stream));
+            PCR_HIP(ctx, hipMemcpyAsync(dab_out + a, J.dab, 8 * (size_t)J.na, hipMemcpyDeviceToHost, ctx->stream));
+            if (mutual_filter) {
+                PCR_HIP(ctx, hipMemcpyAsync(ji_out + b, J.ji, 4 * (size_t)J.nb, hipMemcpyDeviceToHost, ctx->stream));
+                PCR_HIP(ctx, hipMemcpyAsync(dba_out + b, J.dba, 8 * (size_t)J.nb, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            PCR_HIP(ctx, hipMemcpyAsync(corr_out + 2 * a, J.corr, 8 * (size_t)J.na, hipMemcpyDeviceToHost, ctx->stream));
+            PCR_HIP(ctx, hipMemcpyAsync(m_out + p, J.m, 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        PCR_HIP(ctx, pcr_sync(ctx->stream));   // (before the pool goes back)
+    }
+    while (!S.chunks.empty()) S.chunks.pop_front();
+    return PCR_OK;
 }

@@ -53,3 +53,20 @@ def test_voxel_down_sample_properties(og):
     assert len(np.unique(cells, axis=0)) == len(out)         # one centroid per occupied voxel, inside its voxel
     assert len(out) == len(np.unique(np.floor((p - mn) / 2.0), axis=0))
     assert np.allclose(out.mean(axis=0), p.mean(axis=0), atol=0.2)
+
+
+def test_vectorised_pair_features_are_the_scalar_ones(og):
+    """The FPFH restatement computes its pair features for all pairs at once (_pair_features_many); pair_features is the same
+    definition pair by pair.  They must agree bit for bit, degenerate pairs (coincident points, a normal along the line) included."""
+    rng = np.random.default_rng(12)
+    p1, p2 = rng.uniform(-5, 5, (400, 3)), rng.uniform(-5, 5, (400, 3))
+    n1, n2 = rng.normal(size=(400, 3)), rng.normal(size=(400, 3))
+    n1, n2 = n1 / np.linalg.norm(n1, axis=1)[:, None], n2 / np.linalg.norm(n2, axis=1)[:, None]
+    p2[:5] = p1[:5]                                            # zero length
+    p1[5:10], p2[5:10], n1[5:10], n2[5:10] = 0.0, [0, 0, 2.0], [0, 0, 1.0], [0, 0, 1.0]   # d parallel to u: no frame
+    p2[10:20] = np.round(p1[10:20]) + [1, 0, 0]                # lattice-like pairs
+    p1[10:20] = np.round(p1[10:20])
+    many = og._pair_features_many(p1, n1, p2, n2)
+    one = np.array([og.pair_features(p1[i], n1[i], p2[i], n2[i]) for i in range(400)])
+    assert np.array_equal(many, one)
+    assert not many[:10].any()
