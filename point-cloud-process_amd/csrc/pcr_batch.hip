@@ -31,13 +31,12 @@
 #include <vector>
 #include <rocprim/rocprim.hpp>
 #include "pcr_internal.h"
-#include "pcr_grid_dev.h"
+#include "pcr_grid_build_dev.h"
 #include "pcr_icp_step.h"
 #include "pcr_sort.h"
 
 constexpr int SLOT = 256;                 // records per block of the set-up kernels; cloud slots are whole blocks
 constexpr unsigned int MIN_CAP = 256;     // smallest table of the pools: every block of 256 pool slots belongs to one table
-constexpr unsigned long long MORTON_BIAS3 = 7ull << 60;   // spread21(PCR_COORD_BIAS) on x, y and z
 
 struct batch_cloud {          // one per cloud of a sub-batch: sources [0, m), targets [m, 2m)
     unsigned long long off;   // first record slot (multiple of SLOT)
@@ -60,10 +59,6 @@ struct batch_plan {           // device: totals and prefix offsets written by th
     unsigned int overflow;
     unsigned int pad;
 };
-
-__device__ inline unsigned int next_pow2_dev(unsigned int v) {
-    return v <= 1 ? 1u : 1u << (32 - __clz((int)(v - 1)));
-}
 
 // cloud of a block of SLOT records: clouds' slots are whole blocks, so the answer is uniform over the block
 __device__ inline int cloud_of_block(const batch_cloud* __restrict__ cl, int n_clouds, unsigned long long first) {
@@ -101,13 +96,7 @@ batch_keys_kernel(float* xyz_dev, const batch_cloud* __restrict__ cl, int n_clou
             const float* const p = C.src + 3 * (i - C.off);
             const float x = p[0], y = p[1], z = p[2];
             if (xyz_dev + 3 * i != p) { xyz_dev[3 * i] = x; xyz_dev[3 * i + 1] = y; xyz_dev[3 * i + 2] = z; }
-            if (i - C.off < (unsigned long long)C.n) {
-            bool clamped = false;
-            const unsigned long long cx = (unsigned long long)cell_coord((double)x, C.lo[0], C.inv, &clamped);
-            const unsigned long long cy = (unsigned long long)cell_coord((double)y, C.lo[1], C.inv, &clamped);
-            const unsigned long long cz = (unsigned long long)cell_coord((double)z, C.lo[2], C.inv, &clamped);
-            k = (spread21(cx) | (spread21(cy) << 1) | (spread21(cz) << 2)) & mask;
-            }
+            if (i - C.off < (unsigned long long)C.n) k = morton_key((double)x, (double)y, (double)z, C.lo[0], C.lo[1], C.lo[2], C.inv) & mask;
         }
         keys[i] = ((unsigned long long)c << mbits) | k;
         vals[i] = (unsigned int)i;
@@ -153,12 +142,7 @@ batch_count_kernel(const unsigned long long* __restrict__ keys, const batch_clou
     const bool valid = li < (unsigned long long)cl[c].n;
     const unsigned long long mask = (1ull << mbits) - 1ull;
     const unsigned long long k = valid ? (keys[i] & mask) : 0ull, kp = (valid && li > 0) ? (keys[i - 1] & mask) : 0ull;
-    const int levels = tg[t].levels;
-    for (int l = 0; l < levels; ++l) {
-        const bool start = valid && (li == 0 || (k >> (6 * l)) != (kp >> (6 * l)));
-        const unsigned long long b = __ballot(start);
-        if (b && (threadIdx.x & 63) == 0) atomicAdd(&counts[t * PCR_MAX_LEVELS + l], (unsigned int)__popcll(b));
-    }
+    count_run_starts(k, kp, li, valid, tg[t].levels, counts + t * PCR_MAX_LEVELS);
 }
 
 // ONE block: capacities of every (target, level) table from the counts, exclusive prefix over all of them = offsets into the two
@@ -177,11 +161,9 @@ batch_plan_kernel(const unsigned int* __restrict__ counts, const batch_cloud* __
         if (e < n_e) {
             const int t = e / PCR_MAX_LEVELS, l = e % PCR_MAX_LEVELS;
             if (l < tg[t].levels) {
-                const unsigned int cnt = counts[e];
-                cap = next_pow2_dev(cnt * 4 + 4);    // load factor <= 0.25 (pcr_grid_build)
-                if (cap < MIN_CAP) cap = MIN_CAP;
-                bcap = next_pow2_dev(cnt * 2 + 4);
-                if (bcap < MIN_CAP) bcap = MIN_CAP;
+                const pcr_table_caps c = pcr_table_caps_of(counts[e], MIN_CAP);   // pcr_grid_build's rule
+                cap = c.cap;
+                bcap = c.bcap;
             }
         }
         s_c[threadIdx.x] = cap;
@@ -239,13 +221,7 @@ batch_init_tables_kernel(pcr_cell_slot* __restrict__ cell_pool, pcr_block_slot* 
                          const pcr_batch_pair* __restrict__ pairs, int m, unsigned int* __restrict__ tile_pair, unsigned int n_tiles) {
     if (plan->overflow) return;
     const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, t0 = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned long long nc = plan->used_cells, nb = plan->used_blocks;
-    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
-    u2* cp = reinterpret_cast<u2*>(cell_pool);
-    for (unsigned long long i = t0; i < nc; i += stride) cp[i] = u2{~0ull, ~0ull};
-    u2* bp = reinterpret_cast<u2*>(block_pool);
-    for (unsigned long long i = t0; i < 2 * nb; i += stride)
-        bp[i] = (i & 1) ? u2{0ull, 0ull} : u2{PCR_EMPTY_KEY, 0x00000000ffffffffull};   // key | start = ~0, flags = 0 | cnt[8] = 0
+    clear_pools(cell_pool, plan->used_cells, block_pool, plan->used_blocks, t0, stride);
     // tile -> pair: the sources' slots are whole tiles, in pair order
     for (unsigned long long tl = t0; tl < n_tiles; tl += stride) {
         const unsigned long long rec = tl * 32ull;
@@ -257,19 +233,6 @@ batch_init_tables_kernel(pcr_cell_slot* __restrict__ cell_pool, pcr_block_slot* 
         }
         tile_pair[tl] = (unsigned int)lo;
     }
-}
-
-__device__ inline unsigned int batch_slot_find_or_insert(pcr_cell_slot* tab, unsigned int mask, unsigned long long key, unsigned int h) {
-    unsigned int b = h & mask;
-    for (unsigned int probe = 0; probe <= mask; ++probe) {
-        for (unsigned int k = 0; k < 4; ++k) {
-            const unsigned int slot = b * 4 + k;
-            const unsigned long long old = atomicCAS(&tab[slot].key, PCR_EMPTY_KEY, key);
-            if (old == PCR_EMPTY_KEY || old == key) return slot;
-        }
-        b = (b + 1) & mask;
-    }
-    return 0xffffffffu;
 }
 
 __global__ void __launch_bounds__(SLOT)
@@ -285,27 +248,10 @@ batch_insert_cells_kernel(const unsigned long long* __restrict__ keys, const bat
     const unsigned long long k = (keys[i] & mask) | MORTON_BIAS3;
     const unsigned long long kp = li > 0 ? (keys[i - 1] & mask) | MORTON_BIAS3 : 0ull;
     const unsigned long long kn = li + 1 < n ? (keys[i + 1] & mask) | MORTON_BIAS3 : 0ull;
-    const pcr_grid_view* gv = &pairs[t].gv;
-    const int levels = gv->levels;
-    for (int l = 0; l < levels; ++l) {
-        const unsigned long long ck = k >> (6 * l);
-        const bool start = (li == 0) || (ck != (kp >> (6 * l)));
-        const bool end = (li + 1 == n) || (ck != (kn >> (6 * l)));
-        if (start || end) {
-            const unsigned int X = compact21(ck), Y = compact21(ck >> 1), Z = compact21(ck >> 2);
-            pcr_cell_slot* tab = const_cast<pcr_cell_slot*>(gv->table[l]);
-            const unsigned int h = batch_slot_find_or_insert(tab, gv->mask[l], cell_pack(X, Y, Z), cell_hash(X, Y, Z));
-            if (h != 0xffffffffu) {
-                if (start) tab[h].start = (unsigned int)li;
-                if (end) tab[h].end = (unsigned int)(li + 1);
-            }
-        }
-    }
+    insert_cell_runs(pairs[t].gv, k, kp, kn, li, n);
 }
 
-// The thread at the first point of a cell's run looks its (now complete) slot up and registers the cell in its 2x2x2 block: work
-// proportional to the cells, coalesced key reads.  (One thread per slot of the cell POOL -- four fifths of them empty, a binary
-// search per block of 256 to find the slot's table -- took 0.62 of the 5.1 ms of a 256-pair batch.)
+// blocks from the complete cell tables, by the thread at each cell's first record (register_cell_in_block)
 __global__ void __launch_bounds__(SLOT)
 batch_insert_blocks_kernel(const unsigned long long* __restrict__ keys, const batch_cloud* __restrict__ cl, int n_clouds, int m,
                            const pcr_batch_pair* __restrict__ pairs, unsigned long long first_slot, int mbits, const batch_plan* __restrict__ plan) {
@@ -318,39 +264,10 @@ batch_insert_blocks_kernel(const unsigned long long* __restrict__ keys, const ba
     const unsigned long long mask = (1ull << mbits) - 1ull;
     const unsigned long long k = (keys[i] & mask) | MORTON_BIAS3;
     const unsigned long long kp = li > 0 ? (keys[i - 1] & mask) | MORTON_BIAS3 : 0ull;
-    const pcr_grid_view* gv = &pairs[t].gv;
-    const int levels = gv->levels;
-    for (int l = 0; l < levels; ++l) {
-        const unsigned long long ck = k >> (6 * l);
-        if (li != 0 && ck == (kp >> (6 * l))) break;   // not a run start here: not one on any coarser level either
-        const unsigned int X = compact21(ck), Y = compact21(ck >> 1), Z = compact21(ck >> 2);
-        unsigned int cs = 0, ce = 0;
-        if (!lookup_cell(gv->table[l], gv->mask[l], X, Y, Z, &cs, &ce)) continue;
-        pcr_block_slot* bt = const_cast<pcr_block_slot*>(gv->btable[l]);
-        const unsigned int bmask = gv->bmask[l];
-        const unsigned int BX = X >> 1, BY = Y >> 1, BZ = Z >> 1;
-        const int child = (int)((X & 1) | ((Y & 1) << 1) | ((Z & 1) << 2));
-        const unsigned long long bk = cell_pack(BX, BY, BZ);
-        unsigned int b = cell_hash(BX, BY, BZ) & bmask;
-        for (unsigned int probe = 0; probe <= bmask; ++probe) {
-            const unsigned long long old = atomicCAS(&bt[b].key, PCR_EMPTY_KEY, bk);
-            if (old == PCR_EMPTY_KEY || old == bk) break;
-            b = (b + 1) & bmask;
-        }
-        const unsigned int cnt = ce - cs;
-        if (cnt >= 0xffffu) atomicOr(&bt[b].flags, 1u);
-        bt[b].cnt[child] = (unsigned short)(cnt >= 0xffffu ? 0xffffu : cnt);
-        atomicMin(&bt[b].start, cs);
-    }
+    register_cell_in_block(pairs[t].gv, k, kp, li);
 }
 
 namespace {
-
-unsigned int next_pow2_host(unsigned long long v) {
-    unsigned long long p = 1;
-    while (p < v) p <<= 1;
-    return (unsigned int)p;
-}
 
 using dev_block = pcr_dev_block;
 
@@ -665,9 +582,9 @@ int batch_job::launch() {
                 box *= floor(ldexp(k0, -2 * l)) + 1.0;
             }
             const unsigned long long bound = box < (double)T.n ? (unsigned long long)box : (unsigned long long)T.n;
-            unsigned int cap = next_pow2_host(bound * 4 + 4), bcap = next_pow2_host(bound * 2 + 4);
-            cell_pool_slots += cap < MIN_CAP ? MIN_CAP : cap;
-            block_pool_slots += bcap < MIN_CAP ? MIN_CAP : bcap;
+            const pcr_table_caps c = pcr_table_caps_of(bound, MIN_CAP);
+            cell_pool_slots += c.cap;
+            block_pool_slots += c.bcap;
         }
     }
     memcpy(hp + off_tg, tg.data(), sizeof(batch_target) * m);

@@ -1,4 +1,5 @@
-// Multi-level voxel-hash grid over the target cloud + exact 1-NN search kernels.
+// Multi-level voxel-hash grid over the target cloud: bounding box, Morton lay-out and the build of the tables.  The searches are in
+// pcr_grid_search.hip (ICP passes) and pcr_descent.h (the descent that k-NN, radius, normals, ISS and FPFH share).
 //
 // Layout in HBM (per target cloud, built once per pair; stands in for
 // o3d.geometry.KDTreeFlann(target), Registration/main.py:105):
@@ -7,20 +8,18 @@
 //                     its cell id is key >> 6l, so EVERY level's cell is one contiguous
 //                     run of `sorted` (nested octree property of the Morton order).
 //   * table[l][cap_l] open-addressing hash: level-l cell id -> [start,end) in `sorted`
-//                     (16-B slots, load factor <= 0.5; ~1 MB at level 0 for a KITTI scan,
-//                     i.e. L2-resident).
-// Search (per query, G lanes cooperate): at level l examine the 3x3x3 cells around
-// the query; any point outside that block is >= cell_l away, so a best distance
-// <= cell_l is exact.  Otherwise go one level up (cells 4x larger).  With a gate
-// (max_d2) the climb stops at the first level whose cell covers the gate radius.
-// The voxel binning is the same floor((p-min)/leaf) used by voxel_filter.py:30-32.
+//                     (16-B slots in buckets of 4, load factor <= 0.25; ~1 MB at level 0 for
+//                     a KITTI scan, i.e. L2-resident).
+//   * btable[l]       2x2x2 blocks of level-l cells: one 32-B slot answers eight cell lookups.
+// The device steps of the build are in pcr_grid_build_dev.h, shared with the fused batch (pcr_batch.hip); the kernels here find
+// their record by thread index.  The voxel binning is the same floor((p-min)/leaf) used by voxel_filter.py:30-32.
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "pcr_internal.h"
-#include "pcr_grid_dev.h"
+#include "pcr_grid_build_dev.h"
 #include "pcr_sort.h"
 
 // ------------------------------------------------------------ build kernels
@@ -47,13 +46,9 @@ __global__ void bbox_partial_kernel(const pcr_pt* __restrict__ pts, long long n,
     if (threadIdx.x < 6) part[blockIdx.x * 6 + threadIdx.x] = s[threadIdx.x][0];
 }
 
-
-
-
 // ------------------------------------------------------------ set-up path without fills, copies and table scans
 // Morton keys as sorted by the set-up path: only the key bits that vary over the cloud (pcr_morton_end_bit), in 32 bits when
 // they fit -- the (key, position) sort moves a third less -- else in 64.  full_key() puts the constant bias bits back.
-constexpr unsigned long long MORTON_BIAS3 = 7ull << 60;   // spread21(PCR_COORD_BIAS) on x, y and z
 template <typename K>
 __device__ static inline unsigned long long full_key(K k) { return (unsigned long long)k | MORTON_BIAS3; }
 
@@ -64,11 +59,7 @@ morton_keys_var_kernel(const pcr_pt* __restrict__ pts, long long n, double lox, 
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const pcr_pt p = pts[i];
-    bool cl = false;
-    const unsigned long long cx = (unsigned long long)cell_coord(p.x, lox, inv, &cl);
-    const unsigned long long cy = (unsigned long long)cell_coord(p.y, loy, inv, &cl);
-    const unsigned long long cz = (unsigned long long)cell_coord(p.z, loz, inv, &cl);
-    keys[i] = (K)((spread21(cx) | (spread21(cy) << 1) | (spread21(cz) << 2)) & mask);
+    keys[i] = (K)(morton_key(p.x, p.y, p.z, lox, loy, loz, inv) & mask);
     vals[i] = (unsigned int)i;
 }
 
@@ -87,11 +78,7 @@ gather_count_kernel(const pcr_pt* __restrict__ pts, const unsigned int* __restri
     if (levels <= 0) return;
     __syncthreads();
     const unsigned long long k = i < n ? full_key(keys[i]) : 0ull, kp = (i < n && i > 0) ? full_key(keys[i - 1]) : 0ull;
-    for (int l = 0; l < levels; ++l) {
-        const bool start = i < n && (i == 0 || (k >> (6 * l)) != (kp >> (6 * l)));
-        const unsigned long long b = __ballot(start);
-        if (b && (threadIdx.x & 63) == 0) atomicAdd(&s_cnt[l], (unsigned int)__popcll(b));
-    }
+    count_run_starts(k, kp, (unsigned long long)i, i < n, levels, s_cnt);
     __syncthreads();
     // 64 counters per level (block & 63): a million points are 3 900 blocks, and atomics on ONE word are served at ~90 per
     // microsecond (0.41 ms of 0.78 for a 1 M-point index with one counter per level)
@@ -113,110 +100,33 @@ gather_count_kernel(const pcr_pt* __restrict__ pts, const unsigned int* __restri
     if (threadIdx.x == 0) counts[PCR_MAX_LEVELS * 64] = 0;
 }
 
-// all tables of an index in one launch: cell slots all-ones, block slots {free key, start = ~0, flags = 0, counts = 0}
+// all tables of an index in one launch
 __global__ void __launch_bounds__(256)
 init_pools_kernel(pcr_cell_slot* __restrict__ cell_pool, unsigned long long n_cells, pcr_block_slot* __restrict__ block_pool, unsigned long long n_blocks) {
-    typedef unsigned long long u2 __attribute__((ext_vector_type(2)));
-    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x, t0 = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-    u2* cp = reinterpret_cast<u2*>(cell_pool);
-    for (unsigned long long i = t0; i < n_cells; i += stride) cp[i] = u2{~0ull, ~0ull};
-    u2* bp = reinterpret_cast<u2*>(block_pool);
-    for (unsigned long long i = t0; i < 2 * n_blocks; i += stride) bp[i] = (i & 1) ? u2{0ull, 0ull} : u2{PCR_EMPTY_KEY, 0x00000000ffffffffull};
+    clear_pools(cell_pool, n_cells, block_pool, n_blocks, (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, (unsigned long long)gridDim.x * blockDim.x);
 }
 
-
-
-struct pcr_tables {
-    pcr_cell_slot* t[PCR_MAX_LEVELS];
-    unsigned int mask[PCR_MAX_LEVELS];
-};
-
-// buckets of 4 slots, filled from slot 0; mask = number of buckets - 1
-__device__ static inline unsigned int slot_find_or_insert(pcr_cell_slot* tab, unsigned int mask, unsigned long long key, unsigned int h) {
-    unsigned int b = h & mask;
-    for (unsigned int probe = 0; probe <= mask; ++probe) {
-        for (unsigned int k = 0; k < 4; ++k) {
-            const unsigned int slot = b * 4 + k;
-            unsigned long long old = atomicCAS(&tab[slot].key, PCR_EMPTY_KEY, key);
-            if (old == PCR_EMPTY_KEY || old == key) return slot;
-        }
-        b = (b + 1) & mask;
-    }
-    return 0xffffffffu;  // table full: cannot happen at load factor <= 0.25
-}
-
-
-struct pcr_btables {
-    pcr_block_slot* t[PCR_MAX_LEVELS];
-    unsigned int mask[PCR_MAX_LEVELS];
-    unsigned int cap[PCR_MAX_LEVELS];
-};
-
-
-
-
+// (the view travels as a kernel argument: a wave reads the few words of it that it needs by scalar loads)
 template <typename K>
 __global__ void __launch_bounds__(256)
-insert_cells_var_kernel(const K* __restrict__ keys, long long n, int levels, pcr_tables tabs) {
+insert_cells_var_kernel(const K* __restrict__ keys, long long n, pcr_grid_view v) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const unsigned long long k = full_key(keys[i]);
     const unsigned long long kp = i > 0 ? full_key(keys[i - 1]) : 0ull, kn = i + 1 < n ? full_key(keys[i + 1]) : 0ull;
-    for (int l = 0; l < levels; ++l) {
-        const unsigned long long ck = k >> (6 * l);
-        const bool start = (i == 0) || (ck != (kp >> (6 * l)));
-        const bool end = (i + 1 == n) || (ck != (kn >> (6 * l)));
-        if (start || end) {
-            const unsigned int X = compact21(ck), Y = compact21(ck >> 1), Z = compact21(ck >> 2);
-            const unsigned long long pk = (unsigned long long)X | ((unsigned long long)Y << 21) | ((unsigned long long)Z << 42);
-            const unsigned int h = slot_find_or_insert(tabs.t[l], tabs.mask[l], pk, cell_hash(X, Y, Z));
-            if (h != 0xffffffffu) {
-                if (start) tabs.t[l][h].start = (unsigned int)i;
-                if (end) tabs.t[l][h].end = (unsigned int)(i + 1);
-            }
-        }
-    }
+    insert_cell_runs(v, full_key(keys[i]), kp, kn, (unsigned long long)i, (unsigned long long)n);
 }
 
-// The thread at the first point of a cell's run looks its (now complete) slot up and registers the cell in its 2x2x2 block:
-// work proportional to the cells, coalesced key reads (walking every slot of every table instead -- four fifths of them
-// empty -- took 18.5 us at 120 000 points).  Thread 0 also stores the device copy of the view.
+// Blocks from the complete cell tables (register_cell_in_block).  Thread 0 also stores the device copy of the view.
 template <typename K>
 __global__ void __launch_bounds__(256)
-insert_blocks_var_kernel(const K* __restrict__ keys, long long n, int levels, pcr_tables tabs, pcr_btables bt, pcr_grid_view v, pcr_grid_view* __restrict__ d_view) {
+insert_blocks_var_kernel(const K* __restrict__ keys, long long n, pcr_grid_view v, pcr_grid_view* __restrict__ d_view) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) *d_view = v;
     if (i >= n) return;
-    const unsigned long long k = full_key(keys[i]);
-    const unsigned long long kp = i > 0 ? full_key(keys[i - 1]) : 0ull;
-    for (int l = 0; l < levels; ++l) {
-        const unsigned long long ck = k >> (6 * l);
-        if (i != 0 && ck == (kp >> (6 * l))) break;   // not a run start here: not one on any coarser level either
-        const unsigned int X = compact21(ck), Y = compact21(ck >> 1), Z = compact21(ck >> 2);
-        unsigned int cs = 0, ce = 0;
-        if (!lookup_cell(tabs.t[l], tabs.mask[l], X, Y, Z, &cs, &ce)) continue;
-        const unsigned int BX = X >> 1, BY = Y >> 1, BZ = Z >> 1;
-        const int child = (int)((X & 1) | ((Y & 1) << 1) | ((Z & 1) << 2));
-        const unsigned long long bk = cell_pack(BX, BY, BZ);
-        unsigned int b = cell_hash(BX, BY, BZ) & bt.mask[l];
-        for (unsigned int probe = 0; probe <= bt.mask[l]; ++probe) {
-            const unsigned long long old = atomicCAS(&bt.t[l][b].key, PCR_EMPTY_KEY, bk);
-            if (old == PCR_EMPTY_KEY || old == bk) break;
-            b = (b + 1) & bt.mask[l];
-        }
-        const unsigned int cnt = ce - cs;
-        if (cnt >= 0xffffu) atomicOr(&bt.t[l][b].flags, 1u);
-        bt.t[l][b].cnt[child] = (unsigned short)(cnt >= 0xffffu ? 0xffffu : cnt);
-        atomicMin(&bt.t[l][b].start, cs);
-    }
+    register_cell_in_block(v, full_key(keys[i]), i > 0 ? full_key(keys[i - 1]) : 0ull, (unsigned long long)i);
 }
 
 // ------------------------------------------------------------------- host
-static int next_pow2(unsigned int v) {
-    unsigned int p = 1;
-    while (p < v) p <<= 1;
-    return (int)p;
-}
 
 int pcr_bbox(pcr_ctx* ctx, const pcr_pt* pts, long long n, double lo[3], double hi[3]) {
     const int grid_n = (int)((n + 255) / 256);
@@ -332,27 +242,6 @@ static int grid_build_tables(pcr_ctx* ctx, pcr_index* idx, const sort_scratch* s
                              double cell) {
     const long long n = idx->n;
     int rc;
-    // every level's tables in two allocations (cells, 2x2x2 blocks): one launch initialises them all
-    size_t cell_slots = 0, block_slots = 0;
-    for (int l = 0; l < levels; ++l) {
-        unsigned int cap = (unsigned int)next_pow2(h_counts[l] * 4 + 4);   // slots; load factor <= 0.25
-        if (cap < 16) cap = 16;
-        unsigned int bcap = (unsigned int)next_pow2(h_counts[l] * 2 + 4);  // blocks <= cells: load factor <= 0.5, usually ~0.15
-        if (bcap < 16) bcap = 16;
-        idx->caps[l] = cap;
-        idx->bcaps[l] = bcap;
-        cell_slots += cap;
-        block_slots += bcap;
-    }
-    idx->cell_pool_bytes = sizeof(pcr_cell_slot) * cell_slots;
-    idx->block_pool_bytes = sizeof(pcr_block_slot) * block_slots;
-    if ((rc = pcr_dev_alloc(ctx, idx->cell_pool_bytes, (void**)&idx->cell_pool)) || (rc = pcr_dev_alloc(ctx, idx->block_pool_bytes, (void**)&idx->block_pool)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(pcr_grid_view), (void**)&idx->d_view)))
-        return rc;
-    pcr_tables tabs;
-    pcr_btables bt;
-    memset(&tabs, 0, sizeof(tabs));
-    memset(&bt, 0, sizeof(bt));
     pcr_grid_view& v = idx->view;
     memset(&v, 0, sizeof(v));
     v.pts = idx->sorted;
@@ -364,21 +253,25 @@ static int grid_build_tables(pcr_ctx* ctx, pcr_index* idx, const sort_scratch* s
         v.lo[k] = lo[k];
         v.origin[k] = 0.5 * (lo[k] + hi[k]);
     }
-    size_t co = 0, bo = 0;
+    // every level's tables in two allocations (cells, 2x2x2 blocks): one launch initialises them all
+    size_t cell_slots = 0, block_slots = 0;
     for (int l = 0; l < levels; ++l) {
-        idx->tables[l] = idx->cell_pool + co;
-        idx->btables[l] = idx->block_pool + bo;
-        co += idx->caps[l];
-        bo += idx->bcaps[l];
-        tabs.t[l] = idx->tables[l];
-        tabs.mask[l] = idx->caps[l] / 4 - 1;   // buckets of 4 slots
-        bt.t[l] = idx->btables[l];
-        bt.mask[l] = idx->bcaps[l] - 1;
-        bt.cap[l] = idx->bcaps[l];
-        v.table[l] = idx->tables[l];
-        v.mask[l] = tabs.mask[l];
-        v.btable[l] = idx->btables[l];
-        v.bmask[l] = bt.mask[l];
+        const pcr_table_caps c = pcr_table_caps_of(h_counts[l], 16);
+        v.mask[l] = c.cap / 4 - 1;   // buckets of 4 slots
+        v.bmask[l] = c.bcap - 1;
+        cell_slots += c.cap;
+        block_slots += c.bcap;
+    }
+    idx->cell_pool_bytes = sizeof(pcr_cell_slot) * cell_slots;
+    idx->block_pool_bytes = sizeof(pcr_block_slot) * block_slots;
+    if ((rc = pcr_dev_alloc(ctx, idx->cell_pool_bytes, (void**)&idx->cell_pool)) || (rc = pcr_dev_alloc(ctx, idx->block_pool_bytes, (void**)&idx->block_pool)) ||
+        (rc = pcr_dev_alloc(ctx, sizeof(pcr_grid_view), (void**)&idx->d_view)))
+        return rc;
+    for (size_t l = 0, co = 0, bo = 0; l < (size_t)levels; ++l) {
+        v.table[l] = idx->cell_pool + co;
+        v.btable[l] = idx->block_pool + bo;
+        co += 4 * ((size_t)v.mask[l] + 1);
+        bo += (size_t)v.bmask[l] + 1;
     }
     const int grid_n = (int)((n + 255) / 256);
     const unsigned long long words = cell_slots + 2 * block_slots;
@@ -386,10 +279,10 @@ static int grid_build_tables(pcr_ctx* ctx, pcr_index* idx, const sort_scratch* s
     if (gi > 4 * ctx->cu_count) gi = 4 * ctx->cu_count;
     hipLaunchKernelGGL(init_pools_kernel, dim3(gi < 1 ? 1 : gi), dim3(256), 0, ctx->stream, idx->cell_pool, (unsigned long long)cell_slots, idx->block_pool,
                        (unsigned long long)block_slots);
-    hipLaunchKernelGGL(insert_cells_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, levels, tabs);
+    hipLaunchKernelGGL(insert_cells_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, idx->view);
     // (the device copy of the view -- the search kernels read the few fields a wave needs through a pointer, by scalar loads,
     // instead of carrying its 400 bytes in kernel-argument SGPRs -- is stored by thread 0 of this launch)
-    hipLaunchKernelGGL(insert_blocks_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, levels, tabs, bt, idx->view, idx->d_view);
+    hipLaunchKernelGGL(insert_blocks_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, idx->view, idx->d_view);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
@@ -453,5 +346,4 @@ void pcr_grid_free(pcr_ctx* ctx, pcr_index* idx) {
     if (idx->block_pool) pcr_dev_free(ctx, idx->block_pool, idx->block_pool_bytes);
     idx->cell_pool = nullptr;
     idx->block_pool = nullptr;
-    for (int l = 0; l < PCR_MAX_LEVELS; ++l) idx->tables[l] = nullptr, idx->btables[l] = nullptr;   // (pointers into the pools)
 }
