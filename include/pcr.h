@@ -577,6 +577,12 @@ PCR_API int pcr_timer_stop_ms(pcr_ctx* ctx, double* ms_out);
  * ms_out[4] = summed milliseconds (each slot includes the launch gap in front of it), *passes_out = passes profiled. */
 /* diagnostics: per-block {cycles, work} stamps of the last grid search stage kernels (PCR_DEBUG_STAMPS=1) */
 PCR_API int pcr_debug_read(pcr_ctx* ctx, uint64_t* out, int64_t n_words);
+/* diagnostics of the context's device arena: out[0] = blocks handed out and not yet given back, out[1] = their bytes.  Equal before
+ * and after a call that returned no handle, whatever its status.                                                                  */
+PCR_API int pcr_debug_arena(pcr_ctx* ctx, int64_t out[2]);
+/* diagnostics: the nth next device-scratch allocation on this context is refused (PCR_E_NOMEM), once; nth = 0 disarms.  Only a counter
+ * on the host is tested: nothing is launched and no device call is made to fail.  Not for the batch entry points.             */
+PCR_API int pcr_debug_fail_alloc(pcr_ctx* ctx, int nth);
 PCR_API int pcr_profile_enable(pcr_ctx* ctx, int on);
 /* diagnostics of the LAST correspondence search on this context (Registration/main.py:116-121 is the step they describe):
  * out[0] = queries the brute-force MFMA sweep could not prove and re-did with the exact direct-form sweep;

@@ -303,6 +303,8 @@ SIGNATURES = {
     "pcr_kmeans_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _ip, _lp, _dp]),
     "pcr_cloud_download_rows": (C.c_int, [_vp, _vp, _lp, C.c_int64, _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
+    "pcr_debug_arena": (C.c_int, [_vp, _lp]),
+    "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_read": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
     "pcr_search_stats": (C.c_int, [_vp, _lp]),

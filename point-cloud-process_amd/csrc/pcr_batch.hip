@@ -292,9 +292,9 @@ struct batch_call {
     const pcr_pair_ref* pairs = nullptr;
     int64_t n_pairs = 0;
     std::unique_ptr<cloud_entry[]> cache;
-    // device blocks whose contents later sub-batches read: released when the call ends (ctx, pointer, bytes)
+    // device blocks whose contents later sub-batches read: released when the call ends (ctx, pointer)
     std::mutex keep_mu;
-    struct kept { pcr_ctx* ctx; void* p; size_t bytes; };
+    struct kept { pcr_ctx* ctx; void* p; };
     std::vector<kept> keep;
     const double* T0_of(int64_t i) const { return pairs[i].T0; }
 };
@@ -381,9 +381,8 @@ struct batch_job {
     void release() {   // scratch back to the arena (stream-ordered with what was enqueued)
         if (keep_in && d_in.p) {   // (the call releases it when every sub-batch is done)
             std::lock_guard<std::mutex> g(call->keep_mu);
-            call->keep.push_back({ctx, d_in.p, d_in.bytes});
+            call->keep.push_back({ctx, d_in.p});
             d_in.p = nullptr;
-            d_in.bytes = 0;
             keep_in = false;
         }
         for (dev_block* b : {&d_in, &d_pts, &d_keys, &d_keys2, &d_vals, &d_vals2, &d_tmp, &d_cells, &d_blocks, &d_small, &d_res, &d_prev, &d_cost, &d_items, &d_acc, &d_st, &d_tp}) b->free_now();
@@ -1015,7 +1014,7 @@ int batch_run(pcr_ctx* const* ctxs, int n_ctx, batch_call& call, const pcr_icp_p
         // what later sub-batches read of earlier ones: back to the arenas now that every stream has been waited for
         for (auto& S : subs)
             if (S.job && S.job->own_event) hipEventDestroy(S.job->own_event);
-        for (auto& k : call.keep) pcr_dev_free(k.ctx, k.p, k.bytes);
+        for (auto& k : call.keep) pcr_dev_free(k.ctx, k.p);
         call.keep.clear();
     }
     for (int c = 0; c < n_ctx && c < 64; ++c) ctxs[c]->shared_device = was_shared[c];

@@ -456,8 +456,8 @@ int pcr_brute_build(pcr_ctx* ctx, const pcr_cloud* tgt, pcr_index* idx) {
 }
 
 void pcr_brute_free(pcr_ctx* ctx, pcr_index* idx) {
-    pcr_dev_free(ctx, idx->mfma_a, sizeof(double) * 64 * (idx->n_tiles + BR_PAD));
-    pcr_dev_free(ctx, idx->plain, sizeof(pcr_pt) * idx->n);
+    pcr_dev_free(ctx, idx->mfma_a);
+    pcr_dev_free(ctx, idx->plain);
     idx->mfma_a = nullptr;
     idx->plain = nullptr;
 }
@@ -475,32 +475,19 @@ static int brute_splits(pcr_ctx* ctx, long long nq, long long n_tiles) {
 }
 
 struct brute_scratch {
-    brute_cand* cand = nullptr;
-    brute_res* res = nullptr;
-    unsigned int* flag_list = nullptr;
+    pcr_dev_block cand, res, flag_list;   // brute_cand [splits][nq], brute_res [nq], unsigned int [nq]
     int splits = 0;
-    int64_t nq = 0;
+    explicit brute_scratch(pcr_ctx* ctx) : cand(ctx), res(ctx), flag_list(ctx) {}
 };
-
-static void brute_scratch_free(pcr_ctx* ctx, brute_scratch* sc) {
-    if (sc->cand) pcr_dev_free(ctx, sc->cand, sizeof(brute_cand) * (size_t)sc->splits * sc->nq);
-    if (sc->res) pcr_dev_free(ctx, sc->res, sizeof(brute_res) * (size_t)sc->nq);
-    if (sc->flag_list) pcr_dev_free(ctx, sc->flag_list, sizeof(unsigned int) * (size_t)sc->nq);
-    sc->cand = nullptr; sc->res = nullptr; sc->flag_list = nullptr;
-}
 
 // sweep -> merge -> exact fallback; leaves the per-query exact result in sc->res (query order)
 static int brute_search(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int64_t nq, const pcr_xform* x, double max_d2, bool gate_bounds,
                         brute_scratch* sc) {
     sc->splits = brute_splits(ctx, nq, idx->n_tiles);
-    sc->nq = nq;
     int rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(brute_cand) * (size_t)sc->splits * nq, (void**)&sc->cand)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(brute_res) * (size_t)nq, (void**)&sc->res)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * (size_t)nq, (void**)&sc->flag_list))) {
-        brute_scratch_free(ctx, sc);
+    if ((rc = sc->cand.alloc(sizeof(brute_cand) * (size_t)sc->splits * nq)) || (rc = sc->res.alloc(sizeof(brute_res) * (size_t)nq)) ||
+        (rc = sc->flag_list.alloc(sizeof(unsigned int) * (size_t)nq)))
         return rc;
-    }
     pcr_xform xi;
     pcr_xform_from_T(nullptr, &xi);
     const pcr_xform xx = x ? *x : xi;
@@ -511,16 +498,16 @@ static int brute_search(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int
     pcr_prof_mark(ctx, 0);
     hipLaunchKernelGGL(brute_nn_kernel, grid, dim3(256), 0, ctx->stream, (const double*)idx->mfma_a, (const pcr_pt*)idx->plain,
                        (long long)idx->n, (long long)idx->n_tiles, sc->splits, q, (long long)nq, xx, has_x, ox, oy, oz, idx->brute_rt,
-                       idx->brute_bias, sc->cand);
+                       idx->brute_bias, sc->cand.as<brute_cand>());
     pcr_prof_mark(ctx, 1);
     const int g1 = (int)((nq + 255) / 256);
-    hipLaunchKernelGGL(brute_merge_kernel, dim3(g1), dim3(256), 0, ctx->stream, (const brute_cand*)sc->cand, sc->splits, q, (long long)nq, xx,
-                       has_x, ox, oy, oz, idx->brute_rt, idx->brute_bias, max_d2, gate_bounds ? 1 : 0, sc->res, sc->flag_list, flag_count);
+    hipLaunchKernelGGL(brute_merge_kernel, dim3(g1), dim3(256), 0, ctx->stream, sc->cand.as<const brute_cand>(), sc->splits, q, (long long)nq, xx,
+                       has_x, ox, oy, oz, idx->brute_rt, idx->brute_bias, max_d2, gate_bounds ? 1 : 0, sc->res.as<brute_res>(), sc->flag_list.as<unsigned int>(), flag_count);
     // fixed grid; blocks beyond the (device-side) count leave at once
     const long long want = (nq + BR_XQ - 1) / BR_XQ;
     const int g2 = (int)(want < 4ll * ctx->cu_count ? (want < 1 ? 1 : want) : 4ll * ctx->cu_count);
     hipLaunchKernelGGL(brute_exact_kernel, dim3(g2), dim3(256), 0, ctx->stream, (const pcr_pt*)idx->plain, (long long)idx->n, q, xx, has_x,
-                       (const unsigned int*)sc->flag_list, (const unsigned int*)flag_count, sc->res);
+                       sc->flag_list.as<const unsigned int>(), (const unsigned int*)flag_count, sc->res.as<brute_res>());
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
@@ -528,35 +515,31 @@ static int brute_search(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int
 int pcr_brute_nn1(pcr_ctx* ctx, const pcr_index* idx, const pcr_pt* q, int64_t nq, const pcr_xform* x, double max_d2,
                   int32_t* d_idx, double* d_d2) {
     const bool gated = (max_d2 > 0) && std::isfinite(max_d2);
-    brute_scratch sc;
+    brute_scratch sc(ctx);   // (given back stream-ordered behind the launches below)
     // the nn1 API reports the exact neighbour distance of gated-out queries as well: the gate does not bound the search
     int rc = brute_search(ctx, idx, q, nq, x, max_d2, false, &sc);
     if (rc) return rc;
     pcr_xform xi;
     pcr_xform_from_T(nullptr, &xi);
     const int grid = (int)((nq + 255) / 256);
-    hipLaunchKernelGGL(brute_final_kernel<0>, dim3(grid), dim3(256), 0, ctx->stream, (const brute_res*)sc.res, (pcr_pt*)q, (long long)nq,
+    hipLaunchKernelGGL(brute_final_kernel<0>, dim3(grid), dim3(256), 0, ctx->stream, sc.res.as<const brute_res>(), (pcr_pt*)q, (long long)nq,
                        x ? *x : xi, x ? 1 : 0, (const pcr_pt*)idx->plain, max_d2, gated ? 1 : 0, 0, idx->view.origin[0], idx->view.origin[1],
                        idx->view.origin[2], d_idx, d_d2, (double*)nullptr, pcr_counter(ctx, PCR_CW_BRUTE_FLAGS),
                        pcr_counter(ctx, PCR_CW_BRUTE_FLAGS, 1));
     PCR_HIP(ctx, hipGetLastError());
-    brute_scratch_free(ctx, &sc);
     return PCR_OK;
 }
 
 int pcr_brute_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq, const pcr_xform* x, double max_d2, int write_back,
                        double* d_moments) {
     const bool gated = (max_d2 > 0) && std::isfinite(max_d2);
-    brute_scratch sc;
+    brute_scratch sc(ctx);
     int rc = brute_search(ctx, idx, q, nq, x, max_d2, gated, &sc);
     if (rc) return rc;
     const int grid = (int)((nq + 255) / 256);
-    if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * PCR_NMOM * (size_t)grid))) {
-        brute_scratch_free(ctx, &sc);
-        return rc;
-    }
+    if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * PCR_NMOM * (size_t)grid))) return rc;
     pcr_prof_mark(ctx, 2);
-    hipLaunchKernelGGL(brute_final_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream, (const brute_res*)sc.res, q, (long long)nq, *x, 1,
+    hipLaunchKernelGGL(brute_final_kernel<1>, dim3(grid), dim3(256), 0, ctx->stream, sc.res.as<const brute_res>(), q, (long long)nq, *x, 1,
                        (const pcr_pt*)idx->plain, max_d2, gated ? 1 : 0, write_back, idx->view.origin[0], idx->view.origin[1],
                        idx->view.origin[2], (int*)nullptr, (double*)nullptr, ctx->d_partials, pcr_counter(ctx, PCR_CW_BRUTE_FLAGS),
                        pcr_counter(ctx, PCR_CW_BRUTE_FLAGS, 1));
@@ -565,7 +548,6 @@ int pcr_brute_icp_pass(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq
     pcr_prof_mark(ctx, 4);
     PCR_HIP(ctx, hipGetLastError());
     pcr_prof_finish(ctx);
-    brute_scratch_free(ctx, &sc);
     return PCR_OK;
 }
 

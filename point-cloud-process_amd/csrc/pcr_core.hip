@@ -34,15 +34,15 @@ const char* pcr_strerror(int s) {
 
 const char* pcr_last_error(const pcr_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
-int pcr_ctx_create(int device, pcr_ctx** out) {
+int pcr_ctx_create(int device, pcr_ctx** out) try {
     if (!out) return PCR_E_INVALID;
     *out = nullptr;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return PCR_E_NO_DEVICE;
     if (device < 0 || device >= count) return PCR_E_INVALID;
-    pcr_ctx* c = new pcr_ctx();
+    std::unique_ptr<pcr_ctx> c(new pcr_ctx());   // (given back on the early returns below)
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess) { delete c; return PCR_E_HIP; }
+    if (hipSetDevice(device) != hipSuccess) return PCR_E_HIP;
     // the ICP loop waits for a 160-byte read-back every iteration: spin instead of sleeping on an interrupt
     hipSetDeviceFlags(hipDeviceScheduleSpin);
     hipDeviceProp_t prop;
@@ -51,22 +51,20 @@ int pcr_ctx_create(int device, pcr_ctx** out) {
         snprintf(c->name, sizeof(c->name), "%s (%s)", prop.name, prop.gcnArchName);
         c->hbm_bytes = (int64_t)prop.totalGlobalMem;
     }
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return PCR_E_HIP; }
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return PCR_E_HIP;
     hipEventCreate(&c->ev0);
     hipEventCreate(&c->ev1);
     hipEventCreate(&c->ev2);
     hipEventCreate(&c->ev3);
     c->h_pinned_bytes = 4096;
-    if (hipHostMalloc((void**)&c->h_pinned, c->h_pinned_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        delete c;
+    if (hipHostMalloc((void**)&c->h_pinned, c->h_pinned_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
         return PCR_E_NOMEM;
-    }
     // (device-mapped: small results are WRITTEN there by kernels, see pcr_d2h_small)
-    if (hipHostMalloc(&c->h_state, 8192, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { delete c; return PCR_E_NOMEM; }
-    if (hipHostMalloc(&c->h_small, PCR_SMALL_D2H_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { delete c; return PCR_E_NOMEM; }
-    if (hipMalloc((void**)&c->d_counters, PCR_COUNTER_BYTES) != hipSuccess) { delete c; return PCR_E_NOMEM; }
+    if (hipHostMalloc(&c->h_state, 8192, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return PCR_E_NOMEM;
+    if (hipHostMalloc(&c->h_small, PCR_SMALL_D2H_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return PCR_E_NOMEM;
+    if (hipMalloc((void**)&c->d_counters, PCR_COUNTER_BYTES) != hipSuccess) return PCR_E_NOMEM;
     hipMemsetAsync(c->d_counters, 0, PCR_COUNTER_BYTES, c->stream);
-    if (hipMalloc((void**)&c->d_cell_counts, 4 * (PCR_MAX_LEVELS * 64 + 64)) != hipSuccess) { delete c; return PCR_E_NOMEM; }
+    if (hipMalloc((void**)&c->d_cell_counts, 4 * (PCR_MAX_LEVELS * 64 + 64)) != hipSuccess) return PCR_E_NOMEM;
     hipMemsetAsync(c->d_cell_counts, 0, 4 * (PCR_MAX_LEVELS * 64 + 64), c->stream);
     if (getenv("PCR_DEBUG_STAMPS")) {
         hipMalloc((void**)&c->d_debug, sizeof(unsigned long long) << 20);
@@ -75,15 +73,14 @@ int pcr_ctx_create(int device, pcr_ctx** out) {
     // first arena now, not inside the first upload: a 256-MiB hipMalloc takes milliseconds under the driver's lock, and a
     // dozen fresh contexts paying it inside a timed batch cost more than the batch's kernels
     {
-        void* warm = nullptr;
-        if (pcr_dev_alloc(c, 256, &warm) == PCR_OK) pcr_dev_free(c, warm, 256);
+        pcr_dev_block(c.get()).alloc(256);
         // same for the pinned upload staging buffer (hipHostMalloc pins pages under a lock: ~2 ms)
         if (hipHostMalloc(&c->h_stage, 4u << 20, hipHostMallocMapped) == hipSuccess) c->h_stage_bytes = 4u << 20;
         else c->h_stage = nullptr;
     }
-    *out = c;
+    *out = c.release();
     return PCR_OK;
-}
+} PCR_CATCH((pcr_ctx*)nullptr)
 
 int pcr_ctx_destroy(pcr_ctx* c) {
     if (!c) return PCR_OK;
@@ -129,6 +126,20 @@ int pcr_debug_read(pcr_ctx* c, uint64_t* out, int64_t n) {
     if (!c || !out || !c->d_debug || n > (1 << 20)) return PCR_E_INVALID;
     PCR_HIP(c, pcr_sync(c->stream));
     PCR_HIP(c, hipMemcpy(out, c->d_debug, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+    return PCR_OK;
+}
+
+int pcr_debug_arena(pcr_ctx* c, int64_t out[2]) {
+    if (!c || !out) return PCR_E_INVALID;
+    out[0] = (int64_t)c->live.size();
+    out[1] = 0;
+    for (const pcr_ctx::blk& b : c->live) out[1] += (int64_t)b.sz;
+    return PCR_OK;
+}
+
+int pcr_debug_fail_alloc(pcr_ctx* c, int nth) {
+    if (!c || nth < 0) return PCR_E_INVALID;
+    c->fail_alloc_in = nth;
     return PCR_OK;
 }
 
@@ -364,8 +375,15 @@ void pcr_prof_finish(pcr_ctx* ctx) {
 static const size_t PCR_ARENA_BYTES = 256ull << 20;
 
 int pcr_dev_alloc(pcr_ctx* ctx, size_t bytes, void** out) {
+    if (ctx->fail_alloc_in > 0 && --ctx->fail_alloc_in == 0) {   // pcr_debug_fail_alloc
+        ctx->last_error = "pcr_dev_alloc: refused by pcr_debug_fail_alloc";
+        return PCR_E_NOMEM;
+    }
     if (bytes == 0) bytes = 16;
     bytes = (bytes + 255) & ~size_t(255);
+    // room on the free list for every live block: pcr_dev_free runs in destructors and must not allocate
+    const size_t room = ctx->free_list.size() + ctx->live.size() + 2;
+    if (ctx->free_list.capacity() < room) ctx->free_list.reserve(2 * room);
     int best = -1;
     for (int i = 0; i < (int)ctx->free_list.size(); ++i) {
         size_t sz = ctx->free_list[i].sz;
@@ -401,21 +419,19 @@ int pcr_dev_alloc(pcr_ctx* ctx, size_t bytes, void** out) {
     return PCR_OK;
 }
 
-void pcr_dev_free(pcr_ctx* ctx, void* p, size_t bytes) {
+// The block goes back with its true capacity, which only `live` knows (a recycled block may be larger than what was asked for).
+// A pointer that is not live was not handed out by this context, or was given back already: nothing to return, and nobody relies on it.
+void pcr_dev_free(pcr_ctx* ctx, void* p) {
     if (!p) return;
-    if (bytes == 0) bytes = 16;
-    bytes = (bytes + 255) & ~size_t(255);
-    // the block goes back with its true capacity (a larger recycled block would otherwise lose its tail for good)
     for (int i = (int)ctx->live.size() - 1; i >= 0; --i) {
         if (ctx->live[i].p == p) {
-            bytes = ctx->live[i].sz;
+            // Frees are stream-ordered with later allocations: every user of a block runs on ctx->stream.
+            ctx->free_list.push_back(ctx->live[i]);
             ctx->live[i] = ctx->live.back();
             ctx->live.pop_back();
-            break;
+            return;
         }
     }
-    // Frees are stream-ordered with later allocations: every user of a block runs on ctx->stream.
-    ctx->free_list.push_back({p, bytes});
 }
 
 int pcr_ensure_scratch(pcr_ctx* ctx, size_t partial_bytes) {
@@ -546,10 +562,10 @@ static int upload_impl(pcr_ctx* ctx, const S* xyz, int64_t n, int64_t stride, pc
     hipSetDevice(ctx->device);
     static const bool timing = getenv("PCR_UPLOAD_TIMING") != nullptr;   // diagnostics: microseconds per phase to stderr
     const auto t_0 = std::chrono::steady_clock::now();
-    pcr_cloud* c = new pcr_cloud();
+    pcr_cloud_guard c(ctx, new pcr_cloud());
     c->n = n;
     int rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * n, (void**)&c->d);
-    if (rc != PCR_OK) { delete c; return rc; }
+    if (rc != PCR_OK) return rc;
     size_t raw_elems = (size_t)(n - 1) * stride + 3;
     // Caller buffers are pageable: the runtime stages such copies through its own pinned buffers under a lock (~4.5 GB/s in
     // aggregate, however many contexts copy at once), and even copies from pinned memory are submitted through one queue per
@@ -557,7 +573,7 @@ static int upload_impl(pcr_ctx* ctx, const S* xyz, int64_t n, int64_t stride, pc
     // device-mapped buffer, and the expand kernel reads the 12 useful bytes of every record straight from there over PCIe.
     const size_t raw_bytes = raw_elems * sizeof(S);
     const S* d_src = nullptr;     // what the expand kernel reads
-    void* d_raw = nullptr;
+    pcr_dev_block d_raw(ctx);
     if (raw_bytes <= (64u << 20)) {
         if (ctx->h_stage_bytes < raw_bytes) {
             if (ctx->h_stage) hipHostFree(ctx->h_stage);
@@ -592,10 +608,9 @@ static int upload_impl(pcr_ctx* ctx, const S* xyz, int64_t n, int64_t stride, pc
         }
     }
     if (!d_src) {   // very large clouds (or no pinned memory): device staging buffer + the runtime's own copy
-        rc = pcr_dev_alloc(ctx, raw_bytes, &d_raw);
-        if (rc != PCR_OK) { pcr_dev_free(ctx, c->d, sizeof(pcr_pt) * n); delete c; return rc; }
-        PCR_HIP(ctx, hipMemcpyAsync(d_raw, xyz, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_src = (const S*)d_raw;
+        if ((rc = d_raw.alloc(raw_bytes))) return rc;
+        PCR_HIP(ctx, hipMemcpyAsync(d_raw.p, xyz, raw_bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_src = d_raw.as<const S>();
     }
     const auto t_1 = std::chrono::steady_clock::now();
     int block = 256;
@@ -629,8 +644,7 @@ static int upload_impl(pcr_ctx* ctx, const S* xyz, int64_t n, int64_t stride, pc
         fprintf(stderr, "upload n=%lld stride=%lld: host copy + box %.1f us, expand kernel + sync %.1f us\n", (long long)n, (long long)stride,
                 std::chrono::duration_cast<std::chrono::nanoseconds>(t_1 - t_0).count() / 1e3, std::chrono::duration_cast<std::chrono::nanoseconds>(t_2 - t_1).count() / 1e3);
     }
-    if (d_raw) pcr_dev_free(ctx, d_raw, raw_bytes);
-    *out = c;
+    *out = c.release();
     return PCR_OK;
 }
 
@@ -678,31 +692,31 @@ constexpr int64_t PCR_DOWNLOAD_MAX_ROWS = 4096;   // pcr_cloud_download_rows: ro
 
 extern "C" {
 
-int pcr_cloud_upload_f32(pcr_ctx* ctx, const float* xyz, int64_t n, int64_t stride, pcr_cloud** out) {
+int pcr_cloud_upload_f32(pcr_ctx* ctx, const float* xyz, int64_t n, int64_t stride, pcr_cloud** out) try {
     return upload_impl<float>(ctx, xyz, n, stride, out);
-}
+} PCR_CATCH(ctx)
 
-int pcr_cloud_upload_f64(pcr_ctx* ctx, const double* xyz, int64_t n, int64_t stride, pcr_cloud** out) {
+int pcr_cloud_upload_f64(pcr_ctx* ctx, const double* xyz, int64_t n, int64_t stride, pcr_cloud** out) try {
     return upload_impl<double>(ctx, xyz, n, stride, out);
-}
+} PCR_CATCH(ctx)
 
 int pcr_cloud_download_f64(pcr_ctx* ctx, const pcr_cloud* c, double* out) {
     if (!ctx || !c || !out) return PCR_E_INVALID;
     hipSetDevice(ctx->device);
-    double* d_tmp = nullptr;
-    int rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * c->n, (void**)&d_tmp);
+    pcr_dev_block b_tmp(ctx);
+    int rc = b_tmp.alloc(sizeof(double) * 3 * c->n);
     if (rc != PCR_OK) return rc;
+    double* const d_tmp = b_tmp.as<double>();
     int block = 256;
     int grid = (int)((c->n + block - 1) / block);
     hipLaunchKernelGGL(pack_xyz_kernel, dim3(grid), dim3(block), 0, ctx->stream, (const pcr_pt*)c->d, (long long)c->n, d_tmp);
     PCR_HIP(ctx, hipGetLastError());
     PCR_HIP(ctx, hipMemcpyAsync(out, d_tmp, sizeof(double) * 3 * c->n, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, pcr_sync(ctx->stream));
-    pcr_dev_free(ctx, d_tmp, sizeof(double) * 3 * c->n);
     return PCR_OK;
 }
 
-int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows, int64_t m, double* xyz_out) {
+int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows, int64_t m, double* xyz_out) try {
     if (!ctx || !cloud || !rows || !xyz_out || m < 0 || m > PCR_DOWNLOAD_MAX_ROWS) return PCR_E_INVALID;
     if (m == 0) return PCR_OK;
     const int64_t n = cloud->n;
@@ -722,7 +736,7 @@ int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
     PCR_HIP(ctx, hipMemsetAsync(d_out.p, 0xff, sizeof(double) * 3 * m, ctx->stream));   // NaN: a row no record carries as its id
     if ((rc = pcr_cloud_gather_rows(ctx, cloud, d_rows.as<long long>(), d_rows.as<long long>() + m, m, d_out.as<double>()))) return rc;
     return pcr_d2h_small(ctx, xyz_out, d_out.p, sizeof(double) * 3 * m);
-}
+} PCR_CATCH(ctx)
 
 int64_t pcr_cloud_size(const pcr_cloud* c) { return c ? c->n : 0; }
 int pcr_cloud_reordered(const pcr_cloud* c) { return c && c->morton_sorted ? 1 : 0; }
@@ -730,7 +744,7 @@ int pcr_cloud_reordered(const pcr_cloud* c) { return c && c->morton_sorted ? 1 :
 int pcr_cloud_free(pcr_ctx* ctx, pcr_cloud* c) {
     if (!c) return PCR_OK;
     if (!ctx) return PCR_E_INVALID;
-    pcr_dev_free(ctx, c->d, sizeof(pcr_pt) * c->n);
+    pcr_dev_free(ctx, c->d);
     delete c;
     return PCR_OK;
 }

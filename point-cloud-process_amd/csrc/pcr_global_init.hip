@@ -25,8 +25,8 @@ extern "C" {
 int pcr_prep_free(pcr_ctx* ctx, pcr_prep* p) {
     if (!p) return PCR_OK;
     if (!ctx) return PCR_E_INVALID;
-    if (p->normals) pcr_dev_free(ctx, p->normals, sizeof(double) * 3 * p->n);
-    if (p->fpfh) pcr_dev_free(ctx, p->fpfh, sizeof(double) * 33 * p->n);
+    if (p->normals) pcr_dev_free(ctx, p->normals);
+    if (p->fpfh) pcr_dev_free(ctx, p->fpfh);
     if (p->down) pcr_cloud_free(ctx, p->down);
     delete p;
     return PCR_OK;
@@ -36,12 +36,12 @@ int64_t pcr_prep_size(const pcr_prep* p) { return p ? p->n : 0; }
 const pcr_cloud* pcr_prep_cloud(const pcr_prep* p) { return p ? p->down : nullptr; }
 
 int pcr_preprocess(pcr_ctx* ctx, const pcr_cloud* cloud, double voxel_size, double normal_radius, int normal_max_nn, double fpfh_radius, int fpfh_max_nn,
-                   pcr_prep** out) {
+                   pcr_prep** out) try {
     if (!ctx || !cloud || !out || !prep_params_ok(voxel_size, normal_radius, normal_max_nn, fpfh_radius, fpfh_max_nn)) return PCR_E_INVALID;
     *out = nullptr;
     if (cloud->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
-    pcr_prep* p = new pcr_prep();
+    pcr_owned<pcr_prep, pcr_prep_free> p(ctx, new pcr_prep());
     int rc = pcr_voxel_filter_cloud(ctx, cloud, voxel_size, 2, 0, &p->down);   // mode 2 = Open3D's voxel_down_sample (main.py:35)
     if (rc == PCR_OK) {
         p->n = p->down->n;
@@ -51,10 +51,10 @@ int pcr_preprocess(pcr_ctx* ctx, const pcr_cloud* cloud, double voxel_size, doub
     if (rc == PCR_OK) rc = pcr_hybrid_normals_device(ctx, p->down, normal_radius, normal_max_nn, 1, nullptr, p->normals);
     if (rc == PCR_OK) rc = pcr_fpfh_device(ctx, p->down, p->normals, fpfh_radius, fpfh_max_nn, p->fpfh);
     if (rc == PCR_OK) rc = pcr_read_fail(ctx);
-    if (rc != PCR_OK) { pcr_sync(ctx->stream); pcr_prep_free(ctx, p); return rc; }
-    *out = p;
+    if (rc != PCR_OK) { pcr_sync(ctx->stream); return rc; }
+    *out = p.release();
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 int pcr_prep_download(pcr_ctx* ctx, const pcr_prep* p, double* points, double* normals, double* features) {
     if (!ctx || !p) return PCR_E_INVALID;
@@ -297,8 +297,7 @@ int upload_chunk(init_share& S, size_t k) {
     pcr_pt* down = nullptr;
     unsigned int *vsid = nullptr, *scan_first = nullptr;
     rc = pcr_voxel_downsample_scans(ctx, (const float*)b_xyz.p, (int64_t)P.at, P.ds.data(), c.n_scans, S.g->voxel_size, &down, &vsid, &scan_first, c.first.data(), &c.ng);   // (synchronises)
-    const size_t ng1 = (size_t)(c.ng > 0 ? c.ng : 1);   // (the sizes pcr_voxel_downsample_scans took these three blocks with: ng, ng, n_scans + 1)
-    c.down.adopt(down, sizeof(pcr_pt) * ng1); c.vsid.adopt(vsid, 4 * ng1); c.scan_first.adopt(scan_first, 4 * (size_t)(c.n_scans + 1));
+    c.down.adopt(down); c.vsid.adopt(vsid); c.scan_first.adopt(scan_first);
     if (rc) return rc;
     S.lap("down-sample (all scans)");
     for (int q = 0; q < c.n_scans; ++q) {

@@ -131,14 +131,13 @@ insert_blocks_var_kernel(const K* __restrict__ keys, long long n, pcr_grid_view 
 int pcr_bbox(pcr_ctx* ctx, const pcr_pt* pts, long long n, double lo[3], double hi[3]) {
     const int grid_n = (int)((n + 255) / 256);
     int nb = grid_n < 256 ? grid_n : 256;
-    double* d_part = nullptr;
-    int rc = pcr_dev_alloc(ctx, sizeof(double) * 6 * nb, (void**)&d_part);
-    if (rc) return rc;
-    hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(256), 0, ctx->stream, pts, n, d_part);
     std::vector<double> h_part(6 * nb);
-    PCR_HIP(ctx, hipMemcpyAsync(h_part.data(), d_part, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, ctx->stream));
+    pcr_dev_block d_part(ctx);
+    int rc = d_part.alloc(sizeof(double) * 6 * nb);
+    if (rc) return rc;
+    hipLaunchKernelGGL(bbox_partial_kernel, dim3(nb), dim3(256), 0, ctx->stream, pts, n, d_part.as<double>());
+    PCR_HIP(ctx, hipMemcpyAsync(h_part.data(), d_part.p, sizeof(double) * 6 * nb, hipMemcpyDeviceToHost, ctx->stream));
     PCR_HIP(ctx, pcr_sync(ctx->stream));
-    pcr_dev_free(ctx, d_part, sizeof(double) * 6 * nb);
     for (int k = 0; k < 3; ++k) { lo[k] = DBL_MAX; hi[k] = -DBL_MAX; }
     for (int b = 0; b < nb; ++b)
         for (int k = 0; k < 3; ++k) {
@@ -198,40 +197,27 @@ void pcr_grid_plan(const double lo[3], const double hi[3], long long n, double c
 }
 
 // Keys of the varying Morton bits -> stable sort of (key, position) -> records in sorted order (+ cell counts of `levels` levels
-// in ctx->h_pinned[0..levels), valid after the next stream synchronisation).  The sorted keys stay in *keys_out until sort_scratch_free.
+// in ctx->h_pinned[0..levels), valid after the next stream synchronisation).  The sorted keys stay in sc->keys2 while sc lives.
 struct sort_scratch {
-    void *keys = nullptr, *keys2 = nullptr, *temp = nullptr;
-    unsigned int *vals = nullptr, *vals2 = nullptr;
-    size_t key_bytes = 0, temp_bytes = 0;
-    long long n = 0;
+    pcr_dev_block keys, keys2, vals, vals2, temp;
+    explicit sort_scratch(pcr_ctx* ctx) : keys(ctx), keys2(ctx), vals(ctx), vals2(ctx), temp(ctx) {}
 };
-static void sort_scratch_free(pcr_ctx* ctx, sort_scratch* sc) {
-    if (sc->temp) pcr_dev_free(ctx, sc->temp, sc->temp_bytes);
-    if (sc->keys) pcr_dev_free(ctx, sc->keys, sc->key_bytes);
-    if (sc->keys2) pcr_dev_free(ctx, sc->keys2, sc->key_bytes);
-    if (sc->vals) pcr_dev_free(ctx, sc->vals, sizeof(unsigned int) * sc->n);
-    if (sc->vals2) pcr_dev_free(ctx, sc->vals2, sizeof(unsigned int) * sc->n);
-    *sc = sort_scratch();
-}
 template <typename K>
 static int morton_sort_records(pcr_ctx* ctx, const pcr_pt* in, long long n, const double lo[3], double inv, int end_bit, int levels, pcr_pt* out,
                                sort_scratch* sc) {
     int rc;
-    sc->n = n;
-    sc->key_bytes = sizeof(K) * (size_t)n;
-    if ((rc = pcr_dev_alloc(ctx, sc->key_bytes, &sc->keys)) || (rc = pcr_dev_alloc(ctx, sc->key_bytes, &sc->keys2)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&sc->vals)) || (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&sc->vals2)))
+    if ((rc = sc->keys.alloc(sizeof(K) * (size_t)n)) || (rc = sc->keys2.alloc(sizeof(K) * (size_t)n)) || (rc = sc->vals.alloc(sizeof(unsigned int) * n)) ||
+        (rc = sc->vals2.alloc(sizeof(unsigned int) * n)))
         return rc;
-    K *keys = (K*)sc->keys, *keys2 = (K*)sc->keys2;
+    K *keys = sc->keys.as<K>(), *keys2 = sc->keys2.as<K>();
+    unsigned int *vals = sc->vals.as<unsigned int>(), *vals2 = sc->vals2.as<unsigned int>();
     const int grid_n = (int)((n + 255) / 256);
     const unsigned long long mask = end_bit >= 64 ? ~0ull : (1ull << end_bit) - 1ull;
-    hipLaunchKernelGGL(morton_keys_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, n, lo[0], lo[1], lo[2], inv, mask, keys, sc->vals);
-    PCR_HIP(ctx, pcr_sort_pairs(nullptr, sc->temp_bytes, keys, keys2, sc->vals, sc->vals2, (size_t)n, (unsigned int)end_bit, ctx->stream));
-    if ((rc = pcr_dev_alloc(ctx, sc->temp_bytes, &sc->temp))) return rc;
-    PCR_HIP(ctx, pcr_sort_pairs(sc->temp, sc->temp_bytes, keys, keys2, sc->vals, sc->vals2, (size_t)n, (unsigned int)end_bit, ctx->stream));
+    hipLaunchKernelGGL(morton_keys_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, n, lo[0], lo[1], lo[2], inv, mask, keys, vals);
+    if ((rc = pcr_sort_pairs_arena(ctx, keys, keys2, vals, vals2, (size_t)n, (unsigned int)end_bit, sc->temp))) return rc;
     unsigned int* h_counts_dev = nullptr;
     if (levels > 0) PCR_HIP(ctx, hipHostGetDevicePointer((void**)&h_counts_dev, ctx->h_pinned, 0));
-    hipLaunchKernelGGL(gather_count_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, (const unsigned int*)sc->vals2, (const K*)keys2, n, levels, out,
+    hipLaunchKernelGGL(gather_count_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, (const unsigned int*)vals2, (const K*)keys2, n, levels, out,
                        ctx->d_cell_counts, h_counts_dev);   // zero between builds (the last block leaves them so)
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
@@ -279,10 +265,10 @@ static int grid_build_tables(pcr_ctx* ctx, pcr_index* idx, const sort_scratch* s
     if (gi > 4 * ctx->cu_count) gi = 4 * ctx->cu_count;
     hipLaunchKernelGGL(init_pools_kernel, dim3(gi < 1 ? 1 : gi), dim3(256), 0, ctx->stream, idx->cell_pool, (unsigned long long)cell_slots, idx->block_pool,
                        (unsigned long long)block_slots);
-    hipLaunchKernelGGL(insert_cells_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, idx->view);
+    hipLaunchKernelGGL(insert_cells_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, sc->keys2.as<const K>(), n, idx->view);
     // (the device copy of the view -- the search kernels read the few fields a wave needs through a pointer, by scalar loads,
     // instead of carrying its 400 bytes in kernel-argument SGPRs -- is stored by thread 0 of this launch)
-    hipLaunchKernelGGL(insert_blocks_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, (const K*)sc->keys2, n, idx->view, idx->d_view);
+    hipLaunchKernelGGL(insert_blocks_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, sc->keys2.as<const K>(), n, idx->view, idx->d_view);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
@@ -299,7 +285,7 @@ int pcr_grid_build(pcr_ctx* ctx, const pcr_cloud* tgt, double cell, pcr_index* i
     const double inv = 1.0 / cell;
     const int end_bit = pcr_morton_end_bit(lo, hi, inv);
     if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * n, (void**)&idx->sorted))) return rc;
-    sort_scratch sc;
+    sort_scratch sc(ctx);   // (given back stream-ordered behind the launches below)
     const bool k32 = end_bit <= 32;
     rc = k32 ? morton_sort_records<unsigned int>(ctx, tgt->d, n, lo, inv, end_bit, levels, idx->sorted, &sc)
              : morton_sort_records<unsigned long long>(ctx, tgt->d, n, lo, inv, end_bit, levels, idx->sorted, &sc);
@@ -310,7 +296,6 @@ int pcr_grid_build(pcr_ctx* ctx, const pcr_cloud* tgt, double cell, pcr_index* i
         rc = k32 ? grid_build_tables<unsigned int>(ctx, idx, &sc, levels, h_counts, lo, hi, cell)
                  : grid_build_tables<unsigned long long>(ctx, idx, &sc, levels, h_counts, lo, hi, cell);
     }
-    sort_scratch_free(ctx, &sc);   // (stream-ordered with the launches above)
     return rc;
 }
 
@@ -323,27 +308,26 @@ int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell) {
     const double emax = fmax(hi[0] - lo[0], fmax(hi[1] - lo[1], hi[2] - lo[2]));
     if (!(cell > 0)) cell = emax > 0 ? emax / 1024.0 : 1.0;
     if (cell < emax / 262144.0) cell = emax / 262144.0;
-    pcr_pt* d_out = nullptr;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * n, (void**)&d_out))) return rc;
+    pcr_dev_block d_out(ctx);
+    if ((rc = d_out.alloc(sizeof(pcr_pt) * n))) return rc;
     const int end_bit = pcr_morton_end_bit(lo, hi, 1.0 / cell);
-    sort_scratch sc;
-    rc = end_bit <= 32 ? morton_sort_records<unsigned int>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out, &sc)
-                       : morton_sort_records<unsigned long long>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out, &sc);
-    sort_scratch_free(ctx, &sc);
-    if (rc) { pcr_dev_free(ctx, d_out, sizeof(pcr_pt) * n); return rc; }
-    pcr_dev_free(ctx, c->d, sizeof(pcr_pt) * n);
-    c->d = d_out;
+    sort_scratch sc(ctx);
+    rc = end_bit <= 32 ? morton_sort_records<unsigned int>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out.as<pcr_pt>(), &sc)
+                       : morton_sort_records<unsigned long long>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out.as<pcr_pt>(), &sc);
+    if (rc) return rc;
+    pcr_dev_free(ctx, c->d);   // (the cloud's own block: a member, replaced by the sorted one)
+    c->d = d_out.release<pcr_pt>();
     c->morton_sorted = true;
     return PCR_OK;
 }
 
 void pcr_grid_free(pcr_ctx* ctx, pcr_index* idx) {
-    if (idx->d_view) pcr_dev_free(ctx, idx->d_view, sizeof(pcr_grid_view));
+    if (idx->d_view) pcr_dev_free(ctx, idx->d_view);
     idx->d_view = nullptr;
-    if (idx->sorted) pcr_dev_free(ctx, idx->sorted, sizeof(pcr_pt) * idx->n);
+    if (idx->sorted) pcr_dev_free(ctx, idx->sorted);
     idx->sorted = nullptr;
-    if (idx->cell_pool) pcr_dev_free(ctx, idx->cell_pool, idx->cell_pool_bytes);
-    if (idx->block_pool) pcr_dev_free(ctx, idx->block_pool, idx->block_pool_bytes);
+    if (idx->cell_pool) pcr_dev_free(ctx, idx->cell_pool);
+    if (idx->block_pool) pcr_dev_free(ctx, idx->block_pool);
     idx->cell_pool = nullptr;
     idx->block_pool = nullptr;
 }

@@ -262,7 +262,7 @@ int pcr_ground_select(const int64_t* counts, int32_t n_hyp, int64_t n, double ra
 }
 
 int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* samples, const pcr_ground_params* params, pcr_cloud** outliers_out,
-                            int32_t* outlier_rows_out, uint8_t* inlier_mask_out, int64_t* counts_out, pcr_ground_result* result) {
+                            int32_t* outlier_rows_out, uint8_t* inlier_mask_out, int64_t* counts_out, pcr_ground_result* result) try {
     if (outliers_out) *outliers_out = nullptr;
     if (!ctx || !cloud || !samples || !params || !result) return PCR_E_INVALID;
     if (!std::isfinite(params->tau) || params->n_hyp < 1) return PCR_E_INVALID;
@@ -339,36 +339,24 @@ int pcr_ground_segmentation(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
         return PCR_E_HIP;
     }
     if (inlier_mask_out) PCR_HIP(ctx, hipMemcpyAsync(inlier_mask_out, b_flag.p, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    pcr_cloud* c = nullptr;
+    pcr_cloud_guard c(ctx);
     if (want_compact) {
         if (outliers_out) {
-            c = new pcr_cloud();
+            c.h = new pcr_cloud();
             c->n = m;
-            if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * m, (void**)&c->d))) { delete c; return rc; }
+            if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * m, (void**)&c->d))) return rc;
         }
-        if (outlier_rows_out && (rc = b_rows.alloc(sizeof(int) * m))) { if (c) pcr_cloud_free(ctx, c); return rc; }
+        if (outlier_rows_out && (rc = b_rows.alloc(sizeof(int) * m))) return rc;
         if (m > 0) {
             hipLaunchKernelGGL(ground_scatter_kernel, dim3(grid_n), dim3(GR_BLOCK), 0, ctx->stream, pts, n, b_flag.as<const unsigned char>(), b_pre.as<const unsigned int>(),
-                               b_tiles.as<const unsigned int>(), m, c ? c->d : (pcr_pt*)nullptr, outlier_rows_out ? b_rows.as<int>() : (int*)nullptr);
-            hipError_t e = hipGetLastError();
-            if (e == hipSuccess && outlier_rows_out) e = hipMemcpyAsync(outlier_rows_out, b_rows.p, sizeof(int) * m, hipMemcpyDeviceToHost, ctx->stream);
-            if (e != hipSuccess) {
-                ctx->last_error = std::string("pcr_ground_segmentation: ") + hipGetErrorString(e);
-                if (c) pcr_cloud_free(ctx, c);
-                return PCR_E_HIP;
-            }
+                               b_tiles.as<const unsigned int>(), m, c.h ? c->d : (pcr_pt*)nullptr, outlier_rows_out ? b_rows.as<int>() : (int*)nullptr);
+            PCR_HIP(ctx, hipGetLastError());
+            if (outlier_rows_out) PCR_HIP(ctx, hipMemcpyAsync(outlier_rows_out, b_rows.p, sizeof(int) * m, hipMemcpyDeviceToHost, ctx->stream));
         }
     }
-    if (inlier_mask_out || outlier_rows_out) {   // host buffers are only written during the call
-        const hipError_t e = pcr_sync(ctx->stream);
-        if (e != hipSuccess) {
-            ctx->last_error = std::string("pcr_ground_segmentation: ") + hipGetErrorString(e);
-            if (c) pcr_cloud_free(ctx, c);
-            return PCR_E_HIP;
-        }
-    }
-    if (outliers_out) *outliers_out = c;
+    if (inlier_mask_out || outlier_rows_out) PCR_HIP(ctx, pcr_sync(ctx->stream));   // host buffers are only written during the call
+    if (outliers_out) *outliers_out = c.release();
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 }  // extern "C"

@@ -15,28 +15,23 @@
 
 extern "C" {
 
-int pcr_index_build(pcr_ctx* ctx, const pcr_cloud* target, int kind, double cell, pcr_index** out) {
+int pcr_index_build(pcr_ctx* ctx, const pcr_cloud* target, int kind, double cell, pcr_index** out) try {
     if (!ctx || !target || !out) return PCR_E_INVALID;
     *out = nullptr;
     if (target->n <= 0) return PCR_E_EMPTY;
     if (kind != PCR_INDEX_GRID && kind != PCR_INDEX_BRUTE) return PCR_E_INVALID;
     hipSetDevice(ctx->device);
-    pcr_index* idx = new pcr_index();
+    pcr_index_guard idx(ctx, new pcr_index());
     idx->kind = kind;
     idx->n = target->n;
     memset(&idx->view, 0, sizeof(idx->view));
     int rc = pcr_cloud_bbox(ctx, target, idx->lo, idx->hi);
-    if (rc == PCR_OK) {
-        for (int k = 0; k < 3; ++k) idx->view.origin[k] = 0.5 * (idx->lo[k] + idx->hi[k]);
-        rc = (kind == PCR_INDEX_GRID) ? pcr_grid_build(ctx, target, cell, idx) : pcr_brute_build(ctx, target, idx);
-    }
-    if (rc != PCR_OK) {
-        pcr_index_free(ctx, idx);
-        return rc;
-    }
-    *out = idx;
+    if (rc) return rc;
+    for (int k = 0; k < 3; ++k) idx->view.origin[k] = 0.5 * (idx->lo[k] + idx->hi[k]);
+    if ((rc = (kind == PCR_INDEX_GRID) ? pcr_grid_build(ctx, target, cell, idx.h) : pcr_brute_build(ctx, target, idx.h))) return rc;   // (the guard frees what a failed build leaves)
+    *out = idx.release();
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 int pcr_index_free(pcr_ctx* ctx, pcr_index* idx) {
     if (!idx) return PCR_OK;
@@ -53,28 +48,25 @@ double pcr_index_cell(const pcr_index* idx) { return idx ? idx->cell : 0.0; }
 int64_t pcr_index_size(const pcr_index* idx) { return idx ? idx->n : 0; }
 
 int pcr_nn1(pcr_ctx* ctx, const pcr_index* index, const pcr_cloud* queries, const double* T, double max_d2, int32_t* idx_out,
-            double* d2_out) {
+            double* d2_out) try {
     if (!ctx || !index || !queries || !idx_out || !d2_out) return PCR_E_INVALID;
     hipSetDevice(ctx->device);
     const int64_t nq = queries->n;
-    int32_t* d_idx = nullptr;
-    double* d_d2 = nullptr;
+    pcr_dev_block b_idx(ctx), b_d2(ctx);
     int rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(int32_t) * nq, (void**)&d_idx))) return rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(double) * nq, (void**)&d_d2))) return rc;
+    if ((rc = b_idx.alloc(sizeof(int32_t) * nq)) || (rc = b_d2.alloc(sizeof(double) * nq))) return rc;
+    int32_t* const d_idx = b_idx.as<int32_t>();
+    double* const d_d2 = b_d2.as<double>();
     pcr_xform x;
     if (T) pcr_xform_from_T(T, &x);
     if (index->kind == PCR_INDEX_GRID) rc = pcr_grid_nn1(ctx, index, const_cast<pcr_cloud*>(queries), T ? &x : nullptr, max_d2, d_idx, d_d2);
     else rc = pcr_brute_nn1(ctx, index, queries->d, nq, T ? &x : nullptr, max_d2, d_idx, d_d2);
-    if (rc == PCR_OK) {
-        PCR_HIP(ctx, hipMemcpyAsync(idx_out, d_idx, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP(ctx, hipMemcpyAsync(d2_out, d_d2, sizeof(double) * nq, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP(ctx, pcr_sync(ctx->stream));
-    }
-    pcr_dev_free(ctx, d_idx, sizeof(int32_t) * nq);
-    pcr_dev_free(ctx, d_d2, sizeof(double) * nq);
-    return rc;
-}
+    if (rc) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(idx_out, d_idx, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(d2_out, d_d2, sizeof(double) * nq, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, pcr_sync(ctx->stream));
+    return PCR_OK;
+} PCR_CATCH(ctx)
 
 void pcr_icp_default_params(pcr_icp_params* p) {
     if (!p) return;
@@ -129,29 +121,26 @@ int pcr_icp_finish(pcr_ctx* ctx, pcr_cloud* source, const pcr_icp_params* params
 extern "C" {
 
 int pcr_icp_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const double* T, double max_d2,
-                    double moments_out[18], double origin_out[3], double* sum_d2_out) {
+                    double moments_out[18], double origin_out[3], double* sum_d2_out) try {
     if (!ctx || !source || !index || !moments_out) return PCR_E_INVALID;
     hipSetDevice(ctx->device);
     pcr_xform x;
     pcr_xform_from_T(T, &x);
-    double* d_mom = nullptr;
-    int rc = pcr_dev_alloc(ctx, sizeof(double) * PCR_NMOM, (void**)&d_mom);
+    pcr_dev_block d_mom(ctx);
+    int rc = d_mom.alloc(sizeof(double) * PCR_NMOM);
     if (rc) return rc;
-    rc = icp_pass(ctx, index, const_cast<pcr_cloud*>(source), &x, max_d2, 0, d_mom);
-    if (rc == PCR_OK) {
-        PCR_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, d_mom, sizeof(double) * PCR_NMOM, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP(ctx, pcr_sync(ctx->stream));
-        memcpy(moments_out, ctx->h_pinned, sizeof(double) * 18);
-        if (sum_d2_out) *sum_d2_out = ctx->h_pinned[18];
-        if (origin_out)
-            for (int k = 0; k < 3; ++k) origin_out[k] = index->view.origin[k];
-    }
-    pcr_dev_free(ctx, d_mom, sizeof(double) * PCR_NMOM);
-    return rc;
-}
+    if ((rc = icp_pass(ctx, index, const_cast<pcr_cloud*>(source), &x, max_d2, 0, d_mom.as<double>()))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(ctx->h_pinned, d_mom.p, sizeof(double) * PCR_NMOM, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, pcr_sync(ctx->stream));
+    memcpy(moments_out, ctx->h_pinned, sizeof(double) * 18);
+    if (sum_d2_out) *sum_d2_out = ctx->h_pinned[18];
+    if (origin_out)
+        for (int k = 0; k < 3; ++k) origin_out[k] = index->view.origin[k];
+    return PCR_OK;
+} PCR_CATCH(ctx)
 
 int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const pcr_icp_params* params, const double T0[16],
-            pcr_icp_result* res) {
+            pcr_icp_result* res) try {
     if (!ctx || !source || !index || !params || !T0 || !res) return PCR_E_INVALID;
     if (params->max_iter > PCR_ICP_MAX_LOG) return PCR_E_TOO_MANY_ITERS;
     if (source->n <= 0) return PCR_E_EMPTY;
@@ -205,7 +194,7 @@ int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const pcr_i
     hipEventElapsedTime(&loop_ms, ctx->ev0, ctx->ev1);
     res->device_ms = loop_ms;
     return res->status;
-}
+} PCR_CATCH(ctx)
 
 int pcr_procrustes(const double* A, const double* B, int64_t k, double R_out[9], double t_out[3], double* cost_out) {
     if (!A || !B || !R_out || !t_out) return PCR_E_INVALID;
@@ -251,9 +240,9 @@ int pcr_homo2tq(const double T[16], double out[7]) {
 
 }  // extern "C"
 
-extern "C" int pcr_cloud_prepare(pcr_ctx* ctx, pcr_cloud* cloud, const pcr_index* index) {
+extern "C" int pcr_cloud_prepare(pcr_ctx* ctx, pcr_cloud* cloud, const pcr_index* index) try {
     if (!ctx || !cloud || !index) return PCR_E_INVALID;
     hipSetDevice(ctx->device);
     if (index->kind != PCR_INDEX_GRID) return PCR_OK;  // the brute-force sweep does not care about record order
     return pcr_cloud_morton_sort(ctx, cloud, index->cell);
-}
+} PCR_CATCH(ctx)

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <exception>
+#include <new>
 #include <string>
 #include <vector>
 #include "pcr.h"
@@ -99,6 +101,7 @@ struct pcr_ctx {
     std::vector<blk> live;       // blocks handed out, with their TRUE capacity (a reused block may be larger than asked for)
     std::vector<void*> arenas;   // 256-MiB hipMalloc chunks the blocks are carved from
     size_t arena_cap = 0, arena_used = 0;
+    int fail_alloc_in = 0;       // pcr_debug_fail_alloc: the allocation that many calls ahead is refused, once (0: none)
     unsigned long long flag_seq = 0;   // pcr_wait_flag
     long long arena_grow_count = 0;   // hipMalloc calls for arenas since the context was created, and the host time they took
     double arena_grow_us = 0;
@@ -172,8 +175,19 @@ static inline hipError_t pcr_event_sync(hipEvent_t ev) {
         }                                                                             \
     } while (0)
 
+// Exceptions stop at the C ABI: `int f(...) try { ... } PCR_CATCH(ctx)` around every entry point that builds a host container.
+// Unwinding gives back what the call holds (pcr_dev_block, pcr_owned).
+static inline int pcr_caught(pcr_ctx* ctx) noexcept {
+    try { throw; }
+    catch (const std::bad_alloc&) { return PCR_E_NOMEM; }
+    catch (const std::exception& e) { try { if (ctx) ctx->last_error = e.what(); } catch (...) {} }
+    catch (...) { try { if (ctx) ctx->last_error = "unknown C++ exception"; } catch (...) {} }
+    return PCR_E_HIP;
+}
+#define PCR_CATCH(ctx) catch (...) { return pcr_caught(ctx); }
+
 PCR_HIDDEN int pcr_dev_alloc(pcr_ctx* ctx, size_t bytes, void** out);
-PCR_HIDDEN void pcr_dev_free(pcr_ctx* ctx, void* p, size_t bytes);
+PCR_HIDDEN void pcr_dev_free(pcr_ctx* ctx, void* p);   // (the block's capacity is the allocator's own record)
 // records of a cloud in caller row order (the device copy may be Morton-reordered)
 PCR_HIDDEN int pcr_cloud_rows(pcr_ctx* ctx, const pcr_cloud* c, pcr_pt* d_out);
 // the x, y, z of the records that carry the m caller rows of d_rows_sorted (ascending; repeats allowed) -> d_xyz_out[3 * d_slot[j]]
@@ -184,16 +198,31 @@ PCR_HIDDEN int pcr_cloud_gather_rows(pcr_ctx* ctx, const pcr_cloud* c, const lon
 struct pcr_dev_block {
     pcr_ctx* ctx;
     void* p = nullptr;
-    size_t bytes = 0;
     explicit pcr_dev_block(pcr_ctx* c) : ctx(c) {}
     pcr_dev_block(const pcr_dev_block&) = delete;
     pcr_dev_block& operator=(const pcr_dev_block&) = delete;
-    int alloc(size_t b) { free_now(); bytes = b; return pcr_dev_alloc(ctx, b, &p); }
-    void free_now() { if (p) pcr_dev_free(ctx, p, bytes); p = nullptr; bytes = 0; }
-    void adopt(void* q, size_t b) { free_now(); p = q; bytes = b; }   // a block somebody else took from the arena
+    int alloc(size_t b) { free_now(); return pcr_dev_alloc(ctx, b, &p); }
+    void free_now() { if (p) pcr_dev_free(ctx, p); p = nullptr; }
+    void adopt(void* q) { free_now(); p = q; }   // a block somebody else took from the arena
+    template <typename T = void> T* release() { T* q = (T*)p; p = nullptr; return q; }   // the block is the caller's from here on
     ~pcr_dev_block() { free_now(); }
     template <typename T> T* as() const { return (T*)p; }
 };
+// a handle that a call makes for itself (an uploaded cloud, an index, a result not yet complete): freed on every return path
+// unless released to the caller
+template <typename T, int (*FREE)(pcr_ctx*, T*)>
+struct pcr_owned {
+    pcr_ctx* ctx;
+    T* h = nullptr;
+    explicit pcr_owned(pcr_ctx* c, T* q = nullptr) : ctx(c), h(q) {}
+    pcr_owned(const pcr_owned&) = delete;
+    pcr_owned& operator=(const pcr_owned&) = delete;
+    T* release() { T* q = h; h = nullptr; return q; }
+    ~pcr_owned() { if (h) FREE(ctx, h); }
+    T* operator->() const { return h; }
+};
+using pcr_cloud_guard = pcr_owned<pcr_cloud, pcr_cloud_free>;
+using pcr_index_guard = pcr_owned<pcr_index, pcr_index_free>;
 // d_counters: words 0..1023 small per-subsystem counters; words 1024..2047 the hard-list counters of the grid search
 // (32 counters, one per 128-byte line)
 constexpr int PCR_HARD_COUNTERS = 1024;

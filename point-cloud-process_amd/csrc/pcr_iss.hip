@@ -219,19 +219,17 @@ __global__ void iss_gather_kernel(const pcr_pt* __restrict__ rows, const int* __
 }
 
 extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, double gamma21, double gamma32, double nms_radius,
-                       int max_keypoints, double* lambdas_out, int32_t* counts_out, int32_t* keypoints_out, int* n_keypoints_out) {
+                       int max_keypoints, double* lambdas_out, int32_t* counts_out, int32_t* keypoints_out, int* n_keypoints_out) try {
     if (!ctx || !cloud || !(radius > 0)) return PCR_E_INVALID;
     if (!lambdas_out && !(keypoints_out && n_keypoints_out)) return PCR_E_INVALID;   // nothing asked for
     if (cloud->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
     const int64_t n = cloud->n;
-    pcr_index* idx = nullptr;
-    int rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius * (1.0 + 1e-9), &idx);  // block of 27 cells covers the ball with rounding slack
+    pcr_index_guard idx(ctx);   // (every scratch block and the index go back on every return path)
+    int rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius * (1.0 + 1e-9), &idx.h);  // block of 27 cells covers the ball with rounding slack
     if (rc) return rc;
     // the index may have coarsened the cell (huge extents): the 3x3x3 block then still covers the radius
-    if (idx->cell < radius * (1.0 - 1e-12)) { pcr_index_free(ctx, idx); idx = nullptr; return PCR_E_UNSUPPORTED; }
-    // (every scratch block and the index go back on every return path: ADVICE r3)
-    struct index_guard { pcr_ctx* c; pcr_index*& i; ~index_guard() { if (i) { pcr_index_free(c, i); i = nullptr; } } } idx_guard{ctx, idx};
+    if (idx->cell < radius * (1.0 - 1e-12)) return PCR_E_UNSUPPORTED;
     pcr_dev_block b_counts(ctx), b_lam(ctx);
     if ((rc = b_counts.alloc(sizeof(int) * n)) || (rc = b_lam.alloc(sizeof(double) * 3 * n))) return rc;
     int* const d_counts = b_counts.as<int>();
@@ -239,12 +237,11 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     const unsigned grid = (unsigned)((n * IG + 255) / 256);
     const bool want_kp = keypoints_out && n_keypoints_out;
     const bool dev_nms = want_kp && max_keypoints >= 0 && max_keypoints < ISS_NMS_MAX;   // otherwise the host loop over a heap of the candidates
-    int* d_cand = nullptr;
-    pcr_dev_block b_rec(ctx), b_rec2(ctx), b_tmp(ctx);
+    pcr_dev_block b_cand(ctx), b_rec(ctx), b_tmp(ctx);
     unsigned int* d_cand_count = pcr_counter(ctx, PCR_CW_ISS_CAND);
     if (want_kp) {
         if (dev_nms) { if ((rc = b_rec.alloc(sizeof(iss_cand) * n))) return rc; }
-        else if ((rc = pcr_dev_alloc(ctx, sizeof(int) * n, (void**)&d_cand))) return rc;
+        else if ((rc = b_cand.alloc(sizeof(int) * n))) return rc;
         PCR_HIP(ctx, hipMemsetAsync(d_cand_count, 0, sizeof(unsigned int), ctx->stream));
     }
     // "within radius" is `not (sqrt(d2) > radius)` (the radius query's expression, pcr_knn.hip).  sqrt is monotone and correctly
@@ -253,6 +250,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     double r2_in = radius * radius;
     while (sqrt(r2_in) > radius) r2_in = nextafter(r2_in, 0.0);
     while (sqrt(nextafter(r2_in, INFINITY)) <= radius) r2_in = nextafter(r2_in, INFINITY);
+    int* const d_cand = b_cand.as<int>();   // (null unless the host suppression wants the list)
     hipLaunchKernelGGL(iss_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, r2_in, d_counts);
     hipLaunchKernelGGL(iss_cov_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, r2_in, (const int*)d_counts, d_lam, gamma21,
                        gamma32, d_cand, d_cand_count, b_rec.as<iss_cand>());
@@ -299,17 +297,13 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     }
     std::vector<double> cand_l3(n_cand);
     if (want_kp && n_cand) {   // lambda_3 of the candidates, in list order
-        double* d_l3 = nullptr;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(double) * n_cand, (void**)&d_l3)) == PCR_OK) {
-            hipLaunchKernelGGL(iss_cand_l3_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, ctx->stream, (const double*)d_lam, (const int*)d_cand, n_cand, d_l3);
-            hipError_t e = hipMemcpyAsync(cand_l3.data(), d_l3, sizeof(double) * n_cand, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = pcr_sync(ctx->stream);
-            if (e != hipSuccess) { ctx->last_error = std::string("pcr_iss: ") + hipGetErrorString(e); rc = PCR_E_HIP; }
-            pcr_dev_free(ctx, d_l3, sizeof(double) * n_cand);
-        }
+        pcr_dev_block d_l3(ctx);
+        if ((rc = d_l3.alloc(sizeof(double) * n_cand))) return rc;
+        hipLaunchKernelGGL(iss_cand_l3_kernel, dim3((n_cand + 255) / 256), dim3(256), 0, ctx->stream, (const double*)d_lam, (const int*)d_cand, n_cand, d_l3.as<double>());
+        PCR_HIP(ctx, hipMemcpyAsync(cand_l3.data(), d_l3.p, sizeof(double) * n_cand, hipMemcpyDeviceToHost, ctx->stream));
+        PCR_HIP(ctx, pcr_sync(ctx->stream));
     }
     b_lam.free_now();
-    if (rc) { if (d_cand) pcr_dev_free(ctx, d_cand, sizeof(int) * n); return rc; }
     if (want_kp) {
         // Non-maximum suppression (ISS.py:59-73).  The reference walks the candidates in descending lambda_3 (stable: ties
         // in input order) and, for each one still alive, keeps it and removes everything within nms_radius of it.  A
@@ -320,9 +314,8 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
         std::vector<cand_t> cand(n_cand);
         if (n_cand) {
             std::vector<int> ids(n_cand);
-            hipError_t e = hipMemcpyAsync(ids.data(), d_cand, sizeof(int) * n_cand, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = pcr_sync(ctx->stream);
-            if (e != hipSuccess) { ctx->last_error = std::string("pcr_iss: ") + hipGetErrorString(e); rc = PCR_E_HIP; }
+            PCR_HIP(ctx, hipMemcpyAsync(ids.data(), d_cand, sizeof(int) * n_cand, hipMemcpyDeviceToHost, ctx->stream));
+            PCR_HIP(ctx, pcr_sync(ctx->stream));
             for (unsigned int j = 0; j < n_cand; ++j) cand[j] = cand_t{ids[j], cand_l3[j]};
         }
         auto later = [&](const cand_t& a, const cand_t& b) {  // heap order: a comes AFTER b
@@ -330,16 +323,17 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
         };
         std::make_heap(cand.begin(), cand.end(), later);
         // coordinates of the visited candidates only: fetched in small batches by row id
-        pcr_pt *d_rows = nullptr, *d_batch = nullptr;
-        int* d_ids = nullptr;
+        pcr_dev_block b_rows(ctx), b_batch(ctx), b_ids(ctx);
         constexpr size_t BATCH = 256;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * n, (void**)&d_rows)) == PCR_OK) rc = pcr_cloud_rows(ctx, cloud, d_rows);
-        if (rc == PCR_OK) rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * BATCH, (void**)&d_batch);
-        if (rc == PCR_OK) rc = pcr_dev_alloc(ctx, sizeof(int) * BATCH, (void**)&d_ids);
+        if ((rc = b_rows.alloc(sizeof(pcr_pt) * n)) || (rc = pcr_cloud_rows(ctx, cloud, b_rows.as<pcr_pt>())) || (rc = b_batch.alloc(sizeof(pcr_pt) * BATCH)) ||
+            (rc = b_ids.alloc(sizeof(int) * BATCH)))
+            return rc;
+        pcr_pt *const d_rows = b_rows.as<pcr_pt>(), *const d_batch = b_batch.as<pcr_pt>();
+        int* const d_ids = b_ids.as<int>();
         std::vector<pcr_pt> kept;
         int taken = 0;
         size_t heap_n = cand.size();
-        while (rc == PCR_OK && heap_n > 0) {
+        while (heap_n > 0) {
             // pop the next batch of candidates in order and read their records with one copy each (they are few)
             const size_t batch = std::min<size_t>(heap_n, BATCH);
             std::vector<int> ids(batch);
@@ -348,14 +342,10 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
                 ids[j] = cand[--heap_n].id;
             }
             std::vector<pcr_pt> recs(batch);
-            // (errors leave through the clean-up below: the scratch blocks and the index go back on every path)
-            hipError_t e = hipMemcpyAsync(d_ids, ids.data(), sizeof(int) * batch, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(iss_gather_kernel, dim3(1), dim3((unsigned)BATCH), 0, ctx->stream, (const pcr_pt*)d_rows, (const int*)d_ids, (int)batch, d_batch);
-                e = hipMemcpyAsync(recs.data(), d_batch, sizeof(pcr_pt) * batch, hipMemcpyDeviceToHost, ctx->stream);
-            }
-            if (e == hipSuccess) e = pcr_sync(ctx->stream);
-            if (e != hipSuccess) { ctx->last_error = std::string("pcr_iss (suppression): ") + hipGetErrorString(e); rc = PCR_E_HIP; break; }
+            PCR_HIP(ctx, hipMemcpyAsync(d_ids, ids.data(), sizeof(int) * batch, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(iss_gather_kernel, dim3(1), dim3((unsigned)BATCH), 0, ctx->stream, (const pcr_pt*)d_rows, (const int*)d_ids, (int)batch, d_batch);
+            PCR_HIP(ctx, hipMemcpyAsync(recs.data(), d_batch, sizeof(pcr_pt) * batch, hipMemcpyDeviceToHost, ctx->stream));
+            PCR_HIP(ctx, pcr_sync(ctx->stream));
             bool done = false;
             for (size_t j = 0; j < batch && !done; ++j) {
                 const pcr_pt& c = recs[j];
@@ -372,11 +362,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
             }
             if (done) break;
         }
-        if (d_rows) pcr_dev_free(ctx, d_rows, sizeof(pcr_pt) * n);
-        if (d_batch) pcr_dev_free(ctx, d_batch, sizeof(pcr_pt) * BATCH);
-        if (d_ids) pcr_dev_free(ctx, d_ids, sizeof(int) * BATCH);
-        pcr_dev_free(ctx, d_cand, sizeof(int) * n);
         *n_keypoints_out = taken;
     }
-    return rc;
-}
+    return PCR_OK;
+} PCR_CATCH(ctx)

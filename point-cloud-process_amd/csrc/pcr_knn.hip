@@ -637,7 +637,7 @@ static int small_block(pcr_ctx* ctx, size_t bytes, char** host, char** dev) {
 extern "C" {
 
 int pcr_radius_small(pcr_ctx* ctx, const pcr_index* index, const double* queries, int q, double radius, int64_t cap, int64_t* counts_out,
-                     int32_t* idx_out, double* dist_out) {
+                     int32_t* idx_out, double* dist_out) try {
     if (!ctx || !index || !queries || !counts_out || !idx_out || !dist_out || !(radius >= 0) || q < 1 || q > 64 || cap < 1 || cap > (1 << 20)) return PCR_E_INVALID;
     if (index->kind != PCR_INDEX_GRID) return PCR_E_UNSUPPORTED;
     hipSetDevice(ctx->device);
@@ -669,7 +669,7 @@ int pcr_radius_small(pcr_ctx* ctx, const pcr_index* index, const double* queries
         out += cnt[i];
     }
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t q, int k, int32_t* idx_out, double* dist_out) {
     if (!ctx || !index || !queries || !idx_out || !dist_out || k <= 0) return PCR_E_INVALID;
@@ -835,7 +835,7 @@ int pcr_radius(pcr_ctx* ctx, const pcr_index* index, const double* queries, int6
 // traversal, run on the host over the neighbour lists, so labels match the reference's including its quirks: seeds are
 // popped from the END of the index list, a seed needs >= min_pts neighbours (self included) but a reached point only
 // expands with > min_pts, and a point first popped as a noise seed is never relabelled.
-int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts, int32_t* labels_out, int32_t* n_clusters_out) {
+int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts, int32_t* labels_out, int32_t* n_clusters_out) try {
     if (!ctx || !cloud || !labels_out || !(radius >= 0)) return PCR_E_INVALID;
     const int64_t n = cloud->n;
     if (n <= 0) return PCR_E_EMPTY;
@@ -843,43 +843,31 @@ int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts,
     std::vector<double> xyz(3 * (size_t)n);
     int rc = pcr_cloud_download_f64(ctx, cloud, xyz.data());
     if (rc) return rc;
-    pcr_index* index = nullptr;
-    if ((rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius > 0 ? radius : 0.0, &index))) return rc;
-    double* d_q = nullptr;
-    long long *d_counts = nullptr, *d_offs = nullptr;
-    int* d_idx = nullptr;
-    double* d_dist = nullptr;
     std::vector<long long> counts((size_t)n), offs((size_t)n + 1, 0);
     std::vector<int> nbr;
     const unsigned grid = (unsigned)((n + 3) / 4);
-    do {
-        if ((rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&d_q))) break;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(long long) * n, (void**)&d_counts))) break;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(long long) * (n + 1), (void**)&d_offs))) break;
-        hipMemcpyAsync(d_q, xyz.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
-        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, (const double*)d_q, (long long)n, radius, d_counts,
+    {   // (the index and the scratch blocks live for the device part only)
+        pcr_index_guard index(ctx);
+        if ((rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius > 0 ? radius : 0.0, &index.h))) return rc;
+        pcr_dev_block b_q(ctx), b_counts(ctx), b_offs(ctx), b_idx(ctx), b_dist(ctx);
+        if ((rc = b_q.alloc(sizeof(double) * 3 * n)) || (rc = b_counts.alloc(sizeof(long long) * n)) || (rc = b_offs.alloc(sizeof(long long) * (n + 1)))) return rc;
+        const double* const d_q = b_q.as<const double>();
+        long long *const d_counts = b_counts.as<long long>(), *const d_offs = b_offs.as<long long>();
+        hipMemcpyAsync(b_q.p, xyz.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
+        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius, d_counts,
                            (const long long*)nullptr, (int*)nullptr, (double*)nullptr);
         hipMemcpyAsync(counts.data(), d_counts, sizeof(long long) * n, hipMemcpyDeviceToHost, ctx->stream);
-        if (pcr_sync(ctx->stream) != hipSuccess) { rc = PCR_E_HIP; break; }
+        if (pcr_sync(ctx->stream) != hipSuccess) return PCR_E_HIP;
         for (int64_t i = 0; i < n; ++i) offs[(size_t)i + 1] = offs[(size_t)i] + counts[(size_t)i];
         const long long total = offs[(size_t)n];
-        if ((rc = pcr_dev_alloc(ctx, sizeof(int) * (total + 1), (void**)&d_idx))) break;
-        if ((rc = pcr_dev_alloc(ctx, sizeof(double) * (total + 1), (void**)&d_dist))) break;
+        if ((rc = b_idx.alloc(sizeof(int) * (total + 1))) || (rc = b_dist.alloc(sizeof(double) * (total + 1)))) return rc;
         hipMemcpyAsync(d_offs, offs.data(), sizeof(long long) * (n + 1), hipMemcpyHostToDevice, ctx->stream);
-        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, (const double*)d_q, (long long)n, radius,
-                           (long long*)nullptr, (const long long*)d_offs, d_idx, d_dist);
+        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius,
+                           (long long*)nullptr, (const long long*)d_offs, b_idx.as<int>(), b_dist.as<double>());
         nbr.resize((size_t)total + 1);
-        hipMemcpyAsync(nbr.data(), d_idx, sizeof(int) * total, hipMemcpyDeviceToHost, ctx->stream);
-        if (pcr_sync(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) { rc = PCR_E_HIP; break; }
-        pcr_dev_free(ctx, d_idx, sizeof(int) * (total + 1));
-        pcr_dev_free(ctx, d_dist, sizeof(double) * (total + 1));
-        d_idx = nullptr; d_dist = nullptr;
-    } while (0);
-    if (d_q) pcr_dev_free(ctx, d_q, sizeof(double) * 3 * n);
-    if (d_counts) pcr_dev_free(ctx, d_counts, sizeof(long long) * n);
-    if (d_offs) pcr_dev_free(ctx, d_offs, sizeof(long long) * (n + 1));
-    pcr_index_free(ctx, index);
-    if (rc) return rc;
+        hipMemcpyAsync(nbr.data(), b_idx.p, sizeof(int) * total, hipMemcpyDeviceToHost, ctx->stream);
+        if (pcr_sync(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess) return PCR_E_HIP;
+    }
     // dbscan.py:17-34
     std::vector<char> visited((size_t)n, 0);
     std::vector<int> stack;
@@ -904,6 +892,6 @@ int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts,
     }
     if (n_clusters_out) *n_clusters_out = label + 1;
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 }  // extern "C"

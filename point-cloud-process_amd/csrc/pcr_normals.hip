@@ -175,7 +175,7 @@ normals_kernel(pcr_grid_view gv, long long n, double* __restrict__ normals /* by
 
 extern "C" {
 
-int pcr_pca(pcr_ctx* ctx, const pcr_cloud* cloud, double eigvals_out[3], double eigvecs_out[9], double mean_out[3]) {
+int pcr_pca(pcr_ctx* ctx, const pcr_cloud* cloud, double eigvals_out[3], double eigvecs_out[9], double mean_out[3]) try {
     if (!ctx || !cloud || !eigvals_out || !eigvecs_out) return PCR_E_INVALID;
     if (cloud->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
@@ -183,9 +183,10 @@ int pcr_pca(pcr_ctx* ctx, const pcr_cloud* cloud, double eigvals_out[3], double 
     int grid = (int)((n + 1023) / 1024);
     if (grid > 256) grid = 256;
     if (grid < 1) grid = 1;
-    double* d_part = nullptr;
-    int rc = pcr_dev_alloc(ctx, sizeof(double) * 8 * grid, (void**)&d_part);
+    pcr_dev_block b_part(ctx);
+    int rc = b_part.alloc(sizeof(double) * 8 * grid);
     if (rc) return rc;
+    double* const d_part = b_part.as<double>();
     std::vector<double> h(8 * grid);
     double mean[3] = {0, 0, 0}, S[6] = {0, 0, 0, 0, 0, 0};
     for (int pass = 0; pass < 2; ++pass) {
@@ -202,16 +203,15 @@ int pcr_pca(pcr_ctx* ctx, const pcr_cloud* cloud, double eigvals_out[3], double 
                 for (int k = 0; k < 6; ++k) S[k] += h[8 * b + k];
         }
     }
-    pcr_dev_free(ctx, d_part, sizeof(double) * 8 * grid);
     const double inv = n > 1 ? 1.0 / (double)(n - 1) : NAN;  // np.cov of a single observation is nan too
     for (int k = 0; k < 6; ++k) S[k] *= inv;
     sym3_eig(S, eigvals_out, eigvecs_out);
     if (mean_out)
         for (int k = 0; k < 3; ++k) mean_out[k] = mean[k];
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
-int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out, double* eigvals_out, int32_t* neighbours_out) {
+int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out, double* eigvals_out, int32_t* neighbours_out) try {
     if (!ctx || !cloud || !normals_out || k < 2) return PCR_E_INVALID;
     if (cloud->n <= 0) return PCR_E_EMPTY;
     if (k > NK_MAX) return PCR_E_UNSUPPORTED;
@@ -228,17 +228,17 @@ int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out
     if (e[0] < e[1]) std::swap(e[0], e[1]);
     const double factor = 1.8;
     const double cell = (e[0] * e[1] > 0) ? factor * sqrt((double)k / 5.0 * e[0] * e[1] / (double)n) : 0.0;
-    pcr_index* idx = nullptr;
-    rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, cell, &idx);
+    pcr_index_guard idx(ctx);
+    rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, cell, &idx.h);
     if (rc) return rc;
     if (getenv("PCR_NORMALS_DEBUG")) fprintf(stderr, "pcr_normals: n=%lld k=%d cell=%g\n", (long long)n, k, cell);
-    double *d_nrm = nullptr, *d_ev = nullptr;
-    int* d_nbr = nullptr;
-    unsigned int* d_redo = nullptr;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&d_nrm))) return rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&d_ev))) return rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(int) * (size_t)k * n, (void**)&d_nbr))) return rc;
-    if ((rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&d_redo))) return rc;
+    pcr_dev_block b_nrm(ctx), b_ev(ctx), b_nbr(ctx), b_redo(ctx);
+    if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (rc = b_ev.alloc(sizeof(double) * 3 * n)) || (rc = b_nbr.alloc(sizeof(int) * (size_t)k * n)) ||
+        (rc = b_redo.alloc(sizeof(unsigned int) * n)))
+        return rc;
+    double *const d_nrm = b_nrm.as<double>(), *const d_ev = b_ev.as<double>();
+    int* const d_nbr = b_nbr.as<int>();
+    unsigned int* const d_redo = b_redo.as<unsigned int>();
     unsigned int* d_count = pcr_counter(ctx, PCR_CW_NORMALS_REDO);
     PCR_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
     const unsigned grid = (unsigned)((n + 255) / 256);
@@ -271,7 +271,7 @@ int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out
         }
         std::vector<int32_t> kidx((size_t)k * n_redo);
         std::vector<double> kdist((size_t)k * n_redo);
-        if (rc == PCR_OK) rc = pcr_knn(ctx, idx, q.data(), n_redo, k, kidx.data(), kdist.data());
+        if (rc == PCR_OK) rc = pcr_knn(ctx, idx.h, q.data(), n_redo, k, kidx.data(), kdist.data());
         for (unsigned int r = 0; r < n_redo && rc == PCR_OK; ++r) {
             int cnt = 0;
             double m[3] = {0, 0, 0};
@@ -300,12 +300,7 @@ int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out
             }
         }
     }
-    pcr_dev_free(ctx, d_nrm, sizeof(double) * 3 * n);
-    pcr_dev_free(ctx, d_ev, sizeof(double) * 3 * n);
-    pcr_dev_free(ctx, d_nbr, sizeof(int) * (size_t)k * n);
-    pcr_dev_free(ctx, d_redo, sizeof(unsigned int) * n);
-    pcr_index_free(ctx, idx);
     return rc;
-}
+} PCR_CATCH(ctx)
 
 }  // extern "C"

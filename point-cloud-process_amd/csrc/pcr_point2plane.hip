@@ -212,8 +212,8 @@ double gate_d2(double max_dist) { return (max_dist > 0 && std::isfinite(max_dist
 }  // namespace
 
 void pcr_point2plane_free(pcr_ctx* ctx, pcr_index* idx) {
-    if (idx->normals) pcr_dev_free(ctx, idx->normals, sizeof(double) * 3 * idx->n);
-    if (idx->row_pos) pcr_dev_free(ctx, idx->row_pos, sizeof(int32_t) * idx->n);
+    if (idx->normals) pcr_dev_free(ctx, idx->normals);
+    if (idx->row_pos) pcr_dev_free(ctx, idx->row_pos);
     idx->normals = nullptr;
     idx->row_pos = nullptr;
 }
@@ -230,6 +230,8 @@ int pcr_index_set_normals(pcr_ctx* ctx, pcr_index* index, const double* normals)
     hipSetDevice(ctx->device);
     int rc;
     const bool grid = index->kind == PCR_INDEX_GRID;
+    pcr_dev_block by_row(ctx);   // (taken before the index's own blocks: a refusal here leaves the index as it was)
+    if (grid && (rc = by_row.alloc(sizeof(double) * 3 * n))) return rc;
     if (!index->normals && (rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&index->normals))) return rc;
     if (grid && !index->row_pos && (rc = pcr_dev_alloc(ctx, sizeof(int32_t) * n, (void**)&index->row_pos))) {
         pcr_point2plane_free(ctx, index);
@@ -240,8 +242,6 @@ int pcr_index_set_normals(pcr_ctx* ctx, pcr_index* index, const double* normals)
         PCR_HIP(ctx, pcr_sync(ctx->stream));
         return PCR_OK;
     }
-    pcr_dev_block by_row(ctx);
-    if ((rc = by_row.alloc(sizeof(double) * 3 * n))) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(by_row.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(point2plane_permute_normals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const pcr_pt*)index->sorted,
                        (long long)n, (const double*)by_row.p, index->normals, index->row_pos);
@@ -259,7 +259,7 @@ void pcr_icp_plane_default_params(pcr_icp_plane_params* p) {
     p->max_dist = 0.0;
 }
 
-int pcr_point2plane_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const double* T, double max_dist, double out[29]) {
+int pcr_point2plane_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const double* T, double max_dist, double out[29]) try {
     if (!ctx || !source || !index || !out || !index->normals) return PCR_E_INVALID;
     if (source->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
@@ -271,10 +271,10 @@ int pcr_point2plane_moments(pcr_ctx* ctx, const pcr_cloud* source, const pcr_ind
     if ((rc = p2p_pass(ctx, const_cast<pcr_cloud*>(source), index, T ? T : I, gate_d2(max_dist), &sc, d_out.as<double>(), nullptr, p2p_loop_args{})))
         return rc;
     return pcr_d2h_small(ctx, out, d_out.p, sizeof(double) * P2P_NSUM);
-}
+} PCR_CATCH(ctx)
 
 int pcr_icp_point2plane(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* index, const pcr_icp_plane_params* params, const double T0[16],
-                        pcr_icp_plane_result* res) {
+                        pcr_icp_plane_result* res) try {
     if (!ctx || !source || !index || !params || !T0 || !res) return PCR_E_INVALID;
     if (!index->normals || params->max_iter < 0) return PCR_E_INVALID;
     if (params->max_iter > PCR_ICP_MAX_LOG) return PCR_E_TOO_MANY_ITERS;
@@ -319,7 +319,7 @@ int pcr_icp_point2plane(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* 
     if (rc) return rc;
     if ((rc = pcr_events_ms(ctx, &res->device_ms))) return rc;
     return res->status;
-}
+} PCR_CATCH(ctx)
 
 int pcr_point2plane_solve(const double A_upper[21], const double b[6], double x[6], double U[16]) {
     if (!A_upper || !b || !x || !U) return PCR_E_INVALID;

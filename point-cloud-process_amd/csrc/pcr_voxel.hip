@@ -60,12 +60,6 @@ __global__ void voxel_keys_kernel(const pcr_pt* __restrict__ pts, long long n, d
     }
 }
 
-template <typename K>
-struct head_flag {  // position i starts a group of equal keys
-    const K* keys;
-    __host__ __device__ bool operator()(unsigned int i) const { return i == 0u || keys[i] != keys[i - 1u]; }
-};
-
 // NumPy pairwise_sum over a[k] = coord(pts[perm[start + k]]), k in [0, n), for the three coordinates AT ONCE: every
 // record is gathered once (not once per axis) and the 8 records of an unrolled step are requested together, so a dense
 // voxel costs n/8 dependent memory round trips instead of 3n.  Per axis the additions and their order are exactly
@@ -382,12 +376,13 @@ voxel_emit_big_kernel(const vox_xyz* __restrict__ xyz, const unsigned int* __res
 
 struct voxel_work {
     double mn[3], mx[3], D[3];
-    vox_xyz* xyz = nullptr;         // coordinates in voxel-major order
-    unsigned int* heads = nullptr;  // group start positions
-    unsigned int* n_groups = nullptr;
-    unsigned int* big_list = nullptr;   // voxels too populous for a lane group (voxel_emit_big_kernel), <= n / 65 + 1 entries
+    pcr_dev_block xyz;        // coordinates in voxel-major order (vox_xyz)
+    pcr_dev_block heads;      // group start positions
+    pcr_dev_block big_list;   // voxels too populous for a lane group (voxel_emit_big_kernel), <= n / 65 + 1 entries
+    unsigned int* n_groups = nullptr;   // (counter words of the context)
     unsigned int* big_count = nullptr;
     int64_t n = 0;
+    explicit voxel_work(pcr_ctx* ctx) : xyz(ctx), heads(ctx), big_list(ctx) {}
 };
 
 // sort of (key, row) + group heads + voxel-major coordinates for key type K
@@ -396,47 +391,21 @@ static int voxel_groups(pcr_ctx* ctx, const pcr_cloud* c, double leaf, int end_b
     const long long n = c->n;
     const int grid_n = (int)((n + 255) / 256);
     int rc;
-    K *d_keys = nullptr, *d_keys2 = nullptr;
-    unsigned int *d_vals = nullptr, *d_perm = nullptr;
-    void *d_temp = nullptr, *d_temp2 = nullptr;
-    size_t temp_bytes = 0, temp2 = 0;
-    auto release = [&]() {
-        if (d_temp) pcr_dev_free(ctx, d_temp, temp_bytes);
-        if (d_temp2) pcr_dev_free(ctx, d_temp2, temp2);
-        if (d_keys) pcr_dev_free(ctx, d_keys, sizeof(K) * n);
-        if (d_keys2) pcr_dev_free(ctx, d_keys2, sizeof(K) * n);
-        if (d_vals) pcr_dev_free(ctx, d_vals, sizeof(unsigned int) * n);
-        if (d_perm) pcr_dev_free(ctx, d_perm, sizeof(unsigned int) * n);
-    };
-    if ((rc = pcr_dev_alloc(ctx, sizeof(K) * n, (void**)&d_keys)) || (rc = pcr_dev_alloc(ctx, sizeof(K) * n, (void**)&d_keys2)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&d_vals)) || (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * n, (void**)&d_perm)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(vox_xyz) * n, (void**)&w->xyz)) || (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * (n + 1), (void**)&w->heads)) ||
-        (rc = pcr_dev_alloc(ctx, sizeof(unsigned int) * (n / 65 + 1), (void**)&w->big_list))) {
-        release();
+    pcr_dev_block b_keys(ctx), b_keys2(ctx), b_vals(ctx), b_perm(ctx), b_temp(ctx), b_temp2(ctx);   // (freed stream-ordered behind the launches below)
+    if ((rc = b_keys.alloc(sizeof(K) * n)) || (rc = b_keys2.alloc(sizeof(K) * n)) || (rc = b_vals.alloc(sizeof(unsigned int) * n)) ||
+        (rc = b_perm.alloc(sizeof(unsigned int) * n)) || (rc = w->xyz.alloc(sizeof(vox_xyz) * n)) || (rc = w->heads.alloc(sizeof(unsigned int) * (n + 1))) ||
+        (rc = w->big_list.alloc(sizeof(unsigned int) * (n / 65 + 1))))
         return rc;
-    }
+    K *d_keys = b_keys.as<K>(), *d_keys2 = b_keys2.as<K>();
+    unsigned int *d_vals = b_vals.as<unsigned int>(), *d_perm = b_perm.as<unsigned int>();
     hipLaunchKernelGGL((voxel_keys_kernel<K, KEY>), dim3(grid_n), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, n, w->mn[0], w->mn[1], w->mn[2], leaf, w->D[0],
                        w->D[1], (double*)nullptr, d_keys, d_vals);
-    hipError_t e = pcr_sort_pairs(nullptr, temp_bytes, d_keys, d_keys2, d_vals, d_perm, (size_t)n, (unsigned int)end_bit, ctx->stream);
-    if (e == hipSuccess) rc = pcr_dev_alloc(ctx, temp_bytes, &d_temp);
-    if (e == hipSuccess && rc == PCR_OK) e = pcr_sort_pairs(d_temp, temp_bytes, d_keys, d_keys2, d_vals, d_perm, (size_t)n, (unsigned int)end_bit, ctx->stream);
-    if (e == hipSuccess && rc == PCR_OK) {
-        w->big_count = pcr_counter(ctx, PCR_CW_VOXEL, 1);
-        hipLaunchKernelGGL(voxel_gather_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (const unsigned int*)d_perm, n, w->xyz, w->big_count);
-        // group heads = positions whose key differs from the previous one: one fused flag + scan + scatter (rocprim::select
-        // over a counting iterator with a computed flag), instead of a flag kernel, a scan and a scatter
-        w->n_groups = pcr_counter(ctx, PCR_CW_VOXEL);
-        const head_flag<K> flag_op{d_keys2};
-        auto positions = rocprim::counting_iterator<unsigned int>(0u);
-        auto flags = rocprim::make_transform_iterator(positions, flag_op);
-        e = rocprim::select(nullptr, temp2, positions, flags, w->heads, w->n_groups, (size_t)n, ctx->stream);
-        if (e == hipSuccess) rc = pcr_dev_alloc(ctx, temp2, &d_temp2);
-        if (e == hipSuccess && rc == PCR_OK) e = rocprim::select(d_temp2, temp2, positions, flags, w->heads, w->n_groups, (size_t)n, ctx->stream);
-    }
-    if (e == hipSuccess) e = hipGetLastError();
-    release();   // (stream-ordered with the launches above)
-    if (rc) return rc;
-    if (e != hipSuccess) { ctx->last_error = std::string("voxel filter: ") + hipGetErrorString(e); return PCR_E_HIP; }
+    if ((rc = pcr_sort_pairs_arena(ctx, d_keys, d_keys2, d_vals, d_perm, (size_t)n, (unsigned int)end_bit, b_temp))) return rc;
+    w->big_count = pcr_counter(ctx, PCR_CW_VOXEL, 1);
+    hipLaunchKernelGGL(voxel_gather_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (const unsigned int*)d_perm, n, w->xyz.as<vox_xyz>(), w->big_count);
+    w->n_groups = pcr_counter(ctx, PCR_CW_VOXEL);
+    if ((rc = pcr_group_heads(ctx, (const K*)d_keys2, (size_t)n, w->heads.as<unsigned int>(), w->n_groups, b_temp2))) return rc;
+    PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;
 }
 
@@ -479,15 +448,6 @@ static int voxel_prepare(pcr_ctx* ctx, const pcr_cloud* c, double leaf, double* 
     while ((b >> end_bit) != 0ull) ++end_bit;
     if (end_bit <= 32) return voxel_groups<unsigned int, 0>(ctx, c, leaf, end_bit, w);
     return voxel_groups<unsigned long long, 0>(ctx, c, leaf, end_bit, w);
-}
-
-static void voxel_release(pcr_ctx* ctx, voxel_work* w) {
-    if (w->xyz) pcr_dev_free(ctx, w->xyz, sizeof(vox_xyz) * w->n);
-    if (w->heads) pcr_dev_free(ctx, w->heads, sizeof(unsigned int) * (w->n + 1));
-    if (w->big_list) pcr_dev_free(ctx, w->big_list, sizeof(unsigned int) * (w->n / 65 + 1));
-    w->xyz = nullptr;
-    w->heads = nullptr;
-    w->big_list = nullptr;
 }
 
 // ------------------------------------------------------------------------------------------------ many scans at once
@@ -585,19 +545,11 @@ int pcr_voxel_downsample_scans(pcr_ctx* ctx, const float* d_xyz, int64_t n_pts, 
     unsigned long long *d_keys = b_keys.as<unsigned long long>(), *d_keys2 = b_keys2.as<unsigned long long>();
     hipLaunchKernelGGL(scans_keys_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, d_xyz, n, (const down_scan_dev*)b_sc.as<down_scan_dev>(), n_scans, leaf, LB, d_keys,
                        b_vals.as<unsigned int>());
-    size_t temp_bytes = 0, temp2 = 0;
-    PCR_HIP(ctx, pcr_sort_pairs(nullptr, temp_bytes, d_keys, d_keys2, b_vals.as<unsigned int>(), b_perm.as<unsigned int>(), (size_t)n, (unsigned int)end_bit, ctx->stream));
-    if ((rc = b_temp.alloc(temp_bytes))) return rc;
-    PCR_HIP(ctx, pcr_sort_pairs(b_temp.p, temp_bytes, d_keys, d_keys2, b_vals.as<unsigned int>(), b_perm.as<unsigned int>(), (size_t)n, (unsigned int)end_bit, ctx->stream));
+    if ((rc = pcr_sort_pairs_arena(ctx, d_keys, d_keys2, b_vals.as<unsigned int>(), b_perm.as<unsigned int>(), (size_t)n, (unsigned int)end_bit, b_temp))) return rc;
     unsigned int* const big_count = pcr_counter(ctx, PCR_CW_VOXEL, 1);
     unsigned int* const n_groups = pcr_counter(ctx, PCR_CW_VOXEL);
     hipLaunchKernelGGL(scans_gather_kernel, dim3(grid_n), dim3(256), 0, ctx->stream, d_xyz, (const unsigned int*)b_perm.as<unsigned int>(), n, b_xyz.as<vox_xyz>(), big_count);
-    const head_flag<unsigned long long> flag_op{d_keys2};
-    auto positions = rocprim::counting_iterator<unsigned int>(0u);
-    auto flags = rocprim::make_transform_iterator(positions, flag_op);
-    PCR_HIP(ctx, rocprim::select(nullptr, temp2, positions, flags, b_heads.as<unsigned int>(), n_groups, (size_t)n, ctx->stream));
-    if ((rc = b_temp2.alloc(temp2))) return rc;
-    PCR_HIP(ctx, rocprim::select(b_temp2.p, temp2, positions, flags, b_heads.as<unsigned int>(), n_groups, (size_t)n, ctx->stream));
+    if ((rc = pcr_group_heads(ctx, (const unsigned long long*)d_keys2, (size_t)n, b_heads.as<unsigned int>(), n_groups, b_temp2))) return rc;
     // every voxel of the chunk (the count is only known on the device: the emit kernels stride over it), written into a buffer of the
     // upper bound first
     if ((rc = b_full.alloc(sizeof(pcr_pt) * (size_t)n))) return rc;
@@ -632,40 +584,38 @@ int pcr_voxel_downsample_scans(pcr_ctx* ctx, const float* d_xyz, int64_t n_pts, 
     unsigned int* const d_vsid = b_vs.as<unsigned int>();
     PCR_HIP(ctx, hipMemcpyAsync(d_down, d_full, sizeof(pcr_pt) * (size_t)ng, hipMemcpyDeviceToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemcpyAsync(d_vsid, b_vsid.p, 4 * (size_t)ng, hipMemcpyDeviceToDevice, ctx->stream));
-    b_first.p = nullptr; b_down.p = nullptr; b_vs.p = nullptr;   // the caller's now
-    *down_out = d_down; *vsid_out = d_vsid; *scan_first_out = d_first; *ng_out = ng;
+    *down_out = b_down.release<pcr_pt>(); *vsid_out = b_vs.release<unsigned int>(); *scan_first_out = b_first.release<unsigned int>(); *ng_out = ng;   // the caller's now
     return PCR_OK;
 }
 
 extern "C" {
 
-int pcr_voxel_keys(pcr_ctx* ctx, const double* xyz, int64_t n, double leaf, double* h_out, double D_out[3]) {
+int pcr_voxel_keys(pcr_ctx* ctx, const double* xyz, int64_t n, double leaf, double* h_out, double D_out[3]) try {
     if (!ctx || !xyz || !h_out) return PCR_E_INVALID;
     if (n <= 0) return PCR_E_EMPTY;
-    pcr_cloud* c = nullptr;
-    int rc = pcr_cloud_upload_f64(ctx, xyz, n, 3, &c);
+    pcr_cloud_guard c(ctx);
+    int rc = pcr_cloud_upload_f64(ctx, xyz, n, 3, &c.h);
     if (rc) return rc;
-    double* d_h = nullptr;
-    rc = pcr_dev_alloc(ctx, sizeof(double) * n, (void**)&d_h);
-    voxel_work w;
-    if (rc == PCR_OK) rc = voxel_prepare(ctx, c, leaf, d_h, false, &w);
-    if (rc == PCR_OK) {
-        PCR_HIP(ctx, hipMemcpyAsync(h_out, d_h, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-        PCR_HIP(ctx, pcr_sync(ctx->stream));
-        if (D_out)
-            for (int k = 0; k < 3; ++k) D_out[k] = w.D[k];
-    }
-    if (d_h) pcr_dev_free(ctx, d_h, sizeof(double) * n);
-    pcr_cloud_free(ctx, c);
-    return rc;
-}
+    pcr_dev_block d_h(ctx);
+    if ((rc = d_h.alloc(sizeof(double) * n))) return rc;
+    voxel_work w(ctx);
+    if ((rc = voxel_prepare(ctx, c.h, leaf, d_h.as<double>(), false, &w))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(h_out, d_h.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, pcr_sync(ctx->stream));
+    if (D_out)
+        for (int k = 0; k < 3; ++k) D_out[k] = w.D[k];
+    return PCR_OK;
+} PCR_CATCH(ctx)
 
 static int voxel_filter_impl(pcr_ctx* ctx, const pcr_cloud* in, double leaf, int mode, uint64_t seed, pcr_pt* out_pts, double* out_xyz_dev,
                              int64_t* n_out) {
     if (mode != 0 && mode != 1 && mode != 2) return PCR_E_INVALID;
-    voxel_work w;
+    voxel_work w(ctx);
     int rc = voxel_prepare(ctx, in, leaf, nullptr, true, &w, mode == 2);
-    if (rc) { voxel_release(ctx, &w); return rc; }
+    if (rc) return rc;
+    const vox_xyz* const w_xyz = w.xyz.as<vox_xyz>();
+    unsigned int* const w_heads = w.heads.as<unsigned int>();
+    unsigned int* const w_big = w.big_list.as<unsigned int>();
     // the number of groups is only known on the device: launch for the upper bound (threads past the last emitted voxel
     // leave at once) and read the count once everything is queued -- no host round trip in the middle of the chain
     {
@@ -673,16 +623,16 @@ static int voxel_filter_impl(pcr_ctx* ctx, const pcr_cloud* in, double leaf, int
         long long blocks = (in->n * 8 + block - 1) / block;
         if (blocks > 16ll * ctx->cu_count) blocks = 16ll * ctx->cu_count;
         hipLaunchKernelGGL(voxel_emit_kernel, dim3((unsigned)blocks), dim3(block), 0, ctx->stream,
-                           (const vox_xyz*)w.xyz, (const unsigned int*)w.heads, (const unsigned int*)w.n_groups,
-                           (long long)in->n, mode, (unsigned long long)seed, out_pts, out_xyz_dev, w.big_count, w.big_list);
+                           w_xyz, (const unsigned int*)w_heads, (const unsigned int*)w.n_groups,
+                           (long long)in->n, mode, (unsigned long long)seed, out_pts, out_xyz_dev, w.big_count, w_big);
         if (mode != 1) {
             // what the lane groups left on the list (usually nothing at fine leaves: the blocks read the count and leave)
             long long big_max = in->n / (voxel_big_threshold(mode) + 1) + 1;
             if (mode == 2) big_max = (big_max + 3) / 4;
             if (big_max > 8ll * ctx->cu_count) big_max = 8ll * ctx->cu_count;
-            hipLaunchKernelGGL(voxel_emit_big_kernel, dim3((unsigned)big_max), dim3(256), 0, ctx->stream, (const vox_xyz*)w.xyz, (const unsigned int*)w.heads,
+            hipLaunchKernelGGL(voxel_emit_big_kernel, dim3((unsigned)big_max), dim3(256), 0, ctx->stream, w_xyz, (const unsigned int*)w_heads,
                                (const unsigned int*)w.n_groups, (long long)in->n, mode, out_pts, out_xyz_dev, (const unsigned int*)w.big_count,
-                               (const unsigned int*)w.big_list);
+                               (const unsigned int*)w_big);
         }
         PCR_HIP(ctx, hipGetLastError());
     }
@@ -690,51 +640,42 @@ static int voxel_filter_impl(pcr_ctx* ctx, const pcr_cloud* in, double leaf, int
     { const int rc_n = pcr_d2h_small(ctx, &ng, w.n_groups, sizeof(unsigned int)); if (rc_n) return rc_n; }   // (synchronises)
     const int64_t rows = mode == 2 ? (int64_t)ng : (ng > 0 ? (int64_t)ng - 1 : 0);
     *n_out = rows;
-    voxel_release(ctx, &w);
     return PCR_OK;
 }
 
-int pcr_voxel_filter(pcr_ctx* ctx, const double* xyz, int64_t n, double leaf, int mode, uint64_t seed, double* out_xyz, int64_t* n_out) {
+int pcr_voxel_filter(pcr_ctx* ctx, const double* xyz, int64_t n, double leaf, int mode, uint64_t seed, double* out_xyz, int64_t* n_out) try {
     if (!ctx || !xyz || !out_xyz || !n_out) return PCR_E_INVALID;
     if (n <= 0) return PCR_E_EMPTY;
-    pcr_cloud* c = nullptr;
-    int rc = pcr_cloud_upload_f64(ctx, xyz, n, 3, &c);
+    pcr_cloud_guard c(ctx);
+    int rc = pcr_cloud_upload_f64(ctx, xyz, n, 3, &c.h);
     if (rc) return rc;
-    double* d_out = nullptr;
-    rc = pcr_dev_alloc(ctx, sizeof(double) * 3 * n, (void**)&d_out);
-    if (rc == PCR_OK) rc = voxel_filter_impl(ctx, c, leaf, mode, seed, nullptr, d_out, n_out);
-    if (rc == PCR_OK && *n_out > 0) {
-        PCR_HIP(ctx, hipMemcpyAsync(out_xyz, d_out, sizeof(double) * 3 * (*n_out), hipMemcpyDeviceToHost, ctx->stream));
+    pcr_dev_block d_out(ctx);
+    if ((rc = d_out.alloc(sizeof(double) * 3 * n)) || (rc = voxel_filter_impl(ctx, c.h, leaf, mode, seed, nullptr, d_out.as<double>(), n_out))) return rc;
+    if (*n_out > 0) {
+        PCR_HIP(ctx, hipMemcpyAsync(out_xyz, d_out.p, sizeof(double) * 3 * (*n_out), hipMemcpyDeviceToHost, ctx->stream));
         PCR_HIP(ctx, pcr_sync(ctx->stream));
     }
-    if (d_out) pcr_dev_free(ctx, d_out, sizeof(double) * 3 * n);
-    pcr_cloud_free(ctx, c);
-    return rc;
-}
+    return PCR_OK;
+} PCR_CATCH(ctx)
 
-int pcr_voxel_filter_cloud(pcr_ctx* ctx, const pcr_cloud* in, double leaf, int mode, uint64_t seed, pcr_cloud** out) {
+int pcr_voxel_filter_cloud(pcr_ctx* ctx, const pcr_cloud* in, double leaf, int mode, uint64_t seed, pcr_cloud** out) try {
     if (!ctx || !in || !out) return PCR_E_INVALID;
     *out = nullptr;
     if (in->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
-    pcr_pt* d_pts = nullptr;
-    int rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * in->n, (void**)&d_pts);
+    pcr_dev_block d_pts(ctx);
+    int rc = d_pts.alloc(sizeof(pcr_pt) * in->n);
     if (rc) return rc;
     int64_t rows = 0;
-    rc = voxel_filter_impl(ctx, in, leaf, mode, seed, d_pts, nullptr, &rows);
-    if (rc != PCR_OK || rows == 0) {
-        pcr_dev_free(ctx, d_pts, sizeof(pcr_pt) * in->n);
-        return rc != PCR_OK ? rc : PCR_E_EMPTY;  // a single occupied voxel filters to nothing (voxel_filter.py:42-51)
-    }
+    if ((rc = voxel_filter_impl(ctx, in, leaf, mode, seed, d_pts.as<pcr_pt>(), nullptr, &rows))) return rc;
+    if (rows == 0) return PCR_E_EMPTY;  // a single occupied voxel filters to nothing (voxel_filter.py:42-51)
     // shrink to fit
-    pcr_cloud* c = new pcr_cloud();
+    pcr_cloud_guard c(ctx, new pcr_cloud());
     c->n = rows;
-    rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * rows, (void**)&c->d);
-    if (rc) { delete c; pcr_dev_free(ctx, d_pts, sizeof(pcr_pt) * in->n); return rc; }
-    PCR_HIP(ctx, hipMemcpyAsync(c->d, d_pts, sizeof(pcr_pt) * rows, hipMemcpyDeviceToDevice, ctx->stream));
-    pcr_dev_free(ctx, d_pts, sizeof(pcr_pt) * in->n);
-    *out = c;
+    if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * rows, (void**)&c->d))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(c->d, d_pts.p, sizeof(pcr_pt) * rows, hipMemcpyDeviceToDevice, ctx->stream));
+    *out = c.release();
     return PCR_OK;
-}
+} PCR_CATCH(ctx)
 
 }  // extern "C"

@@ -75,6 +75,16 @@ class Context:
         L.check(L.lib().pcr_search_stats(self.handle, L.lptr(out)), self.handle)
         return {"brute_fallback": int(out[0]), "arena_allocations": int(out[1]), "arena_allocation_us": int(out[2]), "arenas": int(out[3])}
 
+    def arena_live(self):
+        """Diagnostics: (blocks, bytes) of device scratch this context has handed out and not got back."""
+        out = np.zeros(2, dtype=np.int64)
+        L.check(L.lib().pcr_debug_arena(self.handle, L.lptr(out)), self.handle)
+        return int(out[0]), int(out[1])
+
+    def fail_alloc(self, n):
+        """Diagnostics: the n-th next device-scratch allocation on this context fails with PCR_E_NOMEM, once; 0 disarms."""
+        L.check(L.lib().pcr_debug_fail_alloc(self.handle, int(n)), self.handle)
+
     def close(self):
         if self._h:
             L.lib().pcr_ctx_destroy(self._h)
@@ -190,11 +200,13 @@ class TargetIndex:
         self.n = target.n
         self.kind = kind
         h = C.c_void_p()
-        L.check(L.lib().pcr_index_build(ctx.handle, target.handle, self.KINDS[kind], float(cell), C.byref(h)), ctx.handle)
-        self._h = h
-        if self._own_cloud is not None:
-            self._own_cloud.free()
-            self._own_cloud = None
+        self._h = h   # (null until the build has succeeded: free() and __del__ are safe on a half-made object)
+        try:
+            L.check(L.lib().pcr_index_build(ctx.handle, target.handle, self.KINDS[kind], float(cell), C.byref(h)), ctx.handle)
+        finally:
+            if self._own_cloud is not None:
+                self._own_cloud.free()
+                self._own_cloud = None
 
     @property
     def handle(self):
@@ -217,9 +229,11 @@ class TargetIndex:
         if T is not None:
             Tc = L.as_f64(T).reshape(16)
             Tp = L.dptr(Tc)
-        L.check(L.lib().pcr_nn1(self.ctx.handle, self.handle, queries.handle, Tp, float(max_d2), L.iptr(idx), L.dptr(d2)), self.ctx.handle)
-        if own is not None:
-            own.free()
+        try:
+            L.check(L.lib().pcr_nn1(self.ctx.handle, self.handle, queries.handle, Tp, float(max_d2), L.iptr(idx), L.dptr(d2)), self.ctx.handle)
+        finally:
+            if own is not None:
+                own.free()
         return idx, d2
 
     def knn(self, queries, k):
@@ -264,9 +278,11 @@ class TargetIndex:
         o = np.zeros(3)
         s = C.c_double()
         Tc = L.as_f64(np.eye(4) if T is None else T).reshape(16)
-        L.check(L.lib().pcr_icp_moments(self.ctx.handle, source.handle, self.handle, L.dptr(Tc), float(max_d2), L.dptr(m), L.dptr(o), C.byref(s)), self.ctx.handle)
-        if own is not None:
-            own.free()
+        try:
+            L.check(L.lib().pcr_icp_moments(self.ctx.handle, source.handle, self.handle, L.dptr(Tc), float(max_d2), L.dptr(m), L.dptr(o), C.byref(s)), self.ctx.handle)
+        finally:
+            if own is not None:
+                own.free()
         return m, o, s.value
 
     def set_normals(self, normals):

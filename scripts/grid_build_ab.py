@@ -1,7 +1,7 @@
 """A/B of the grid build between two libraries (PCR_LIB_PATH): bench.py's own `setup` figures on the 120k pair and its `batch256`
 compat / tight figures, each library in a fresh process, alternately, RUNS times each.
 
-  python scripts/grid_build_ab.py --parent scripts/bin/libpcr_parent.so --out profiles/grid_build_ab.json [--runs 5]
+  python scripts/grid_build_ab.py --parent scripts/bin/libpcr_parent.so --out profiles/grid_build_ab.json [--runs 5] [--what "the change"]
   python scripts/grid_build_ab.py --one            one run of the library in PCR_LIB_PATH (default: the built one), a JSON line
   python scripts/grid_build_ab.py --prof           the build kernels a few times, for rocprofv3 --kernel-trace --stats
   python scripts/grid_build_ab.py --fold-stats PARENT_kernel_stats.csv NEW_kernel_stats.csv --out profiles/grid_build_kernel_stats.csv
@@ -68,7 +68,7 @@ def fold_stats(parent_csv, new_csv, out):
         print("%-8s %-48s calls %5s avg %9.1f us" % (r[0], r[1][:48], r[2], float(r[3]) / 1e3))
 
 
-def session(parent, runs, out, timeout):
+def session(parent, runs, out, timeout, what):
     libs = (("parent", os.path.abspath(parent)), ("new", os.path.join(ROOT, "point-cloud-process_amd", "libpcr.so")))
     got = {"parent": [], "new": []}
     for r in range(runs):
@@ -81,7 +81,7 @@ def session(parent, runs, out, timeout):
                 sys.exit(f"run {r} of the {tag} library failed (exit {p.returncode}): session ended")
             got[tag].append(json.loads(line[3:]))
             print(tag, r, {k: round(got[tag][-1][k], 5) for k in FIGURES}, flush=True)
-    res = {"what": "A/B of the grid-build refactor (one copy of the table build, csrc/pcr_grid_build_dev.h): bench.py's setup figures (ms, best of "
+    res = {"what": f"A/B of {what}: bench.py's setup figures (ms, best of "
                    "10, 120 000-point pair) and batch256 seconds (best of 8, 256 x 20 000-point pairs, 8 contexts) for the parent commit's library "
                    f"and the new one, {runs} fresh processes each, alternately (parent, new, ...) in one session on one MI355X; margin = the "
                    "parent's own max - min; inside = median(new) - median(parent) <= margin",
@@ -115,6 +115,7 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per child process")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--what", default="the grid-build refactor (one copy of the table build, csrc/pcr_grid_build_dev.h)", help="the change under test, for the record's first line")
     a = ap.parse_args()
     if a.one:
         one()
@@ -123,4 +124,4 @@ if __name__ == "__main__":
     elif a.fold_stats:
         fold_stats(a.fold_stats[0], a.fold_stats[1], a.out or os.path.join(ROOT, "profiles", "grid_build_kernel_stats.csv"))
     else:
-        session(a.parent, a.runs, a.out or os.path.join(ROOT, "profiles", "grid_build_ab.json"), a.timeout)
+        session(a.parent, a.runs, a.out or os.path.join(ROOT, "profiles", "grid_build_ab.json"), a.timeout, a.what)

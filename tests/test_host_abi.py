@@ -26,6 +26,16 @@ def test_library_exports_every_declared_symbol(pcp):
     assert set(L.SIGNATURES) == set(names)
 
 
+def test_arena_diagnostics_are_declared_exported_and_refuse_a_null_context(pcp):
+    L = pcp._lib
+    lib = L.lib()
+    for n in ("pcr_debug_arena", "pcr_debug_fail_alloc"):
+        assert n in _declared_symbols() and n in L.SIGNATURES and hasattr(lib, n)
+    out = np.zeros(2, dtype=np.int64)
+    assert lib.pcr_debug_arena(None, L.lptr(out)) == L.PCR_E_INVALID
+    assert lib.pcr_debug_fail_alloc(None, 1) == L.PCR_E_INVALID
+
+
 def test_no_gpu_means_loud_failure_not_fallback(pcp):
     import torch
 
