@@ -132,7 +132,8 @@ typedef struct pcr_icp_params {
     double max_d2;      /* main.py:103 -> 5 (threshold on SQUARED distance) */
     int32_t mode;       /* PCR_ICP_COMPAT_MAIN | PCR_ICP_TOTAL */
     int32_t r_metric;   /* PCR_RMETRIC_* (template hint icp_template.py:184) */
-    int32_t min_iter;   /* bench only: never break before this many iterations (0 = reference behaviour) */
+    int32_t min_iter;   /* bench only: never break on the thresholds before this many solves (0 = reference behaviour);
+                         * max_iter and too few associations still stop the loop */
     int32_t reserved;
 } pcr_icp_params;
 
@@ -141,7 +142,7 @@ typedef struct pcr_icp_result {
     double T_total[16];    /* composed transform in both modes                          */
     int32_t iters;         /* Procrustes solves performed                               */
     int32_t status;        /* PCR_OK or PCR_E_TOO_FEW_ASSOC                             */
-    int64_t n_assoc;       /* associations of the last solved iteration                 */
+    int64_t n_assoc;       /* associations of the last association pass (< 3: that pass stopped the loop) */
     double cost;           /* ||B - (R A + t)||_F of the last solve (main.py:141)       */
     double mean_d2;        /* mean squared NN distance of the last association pass     */
     double r_diff[PCR_ICP_MAX_LOG]; /* log["R_diff"], icp_template.py:189 */
@@ -149,13 +150,15 @@ typedef struct pcr_icp_result {
     double device_ms;      /* duration of the whole loop on the device: the kernels' own 100-MHz clock, first kernel .. end of the last pass (device-resident loop), HIP events otherwise */
     double nn_kernel_ms;   /* sum of HIP-event times of the pass kernels; 0 unless pcr_profile_enable(ctx, 1) (host loop: always) */
     int32_t nn_launches;   /* launches of the correspondence kernel                     */
-    int32_t reserved;
+    int32_t reserved;      /* diagnostic: 1 when the fused stages of pcr_icp_batch / pcr_register_pairs produced this result, 0 from pcr_icp (and from the batch's per-pair path) */
 } pcr_icp_result;
 
 PCR_API void pcr_icp_default_params(pcr_icp_params* p);
 /* icp_point2point(source, target, transformation) (main.py:97) / ICP (icp_template.py:128).
  * `source` is updated in place exactly like main.py:110 mutates it (COMPAT) or
- * icp_template.py:195-196 (TOTAL).                                            */
+ * icp_template.py:195-196 (TOTAL).  max_iter <= 0: COMPAT returns T = T0, T_total = I and leaves the source alone
+ * (main.py's loop body never runs); TOTAL returns T = T_total = T0 and applies T0 to the source (icp_template.py:146-152
+ * applies the initial pose in front of the loop).  max_iter > PCR_ICP_MAX_LOG: PCR_E_TOO_MANY_ITERS, nothing is written. */
 PCR_API int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* target_index, const pcr_icp_params* params,
                     const double T0[16], pcr_icp_result* result);
 

@@ -222,7 +222,9 @@ def native_register_share(pairs, device=0, streams=8, mode="compat", max_iter=10
             return (table, T_init.reshape(n, 4, 4)) if return_init else table
         T, Tt = res["T"].reshape(n, 4, 4), res["T_total"].reshape(n, 4, 4)
         out = [{"T": T[i], "T_total": Tt[i], "iters": int(res["iters"][i]), "status": int(res["status"][i]), "n_assoc": int(res["n_assoc"][i]),
-                "cost": float(res["cost"][i]), "mean_d2": float(res["mean_d2"][i])} for i in range(n)]
+                "cost": float(res["cost"][i]), "mean_d2": float(res["mean_d2"][i]), "R_diff": res["r_diff"][i, :res["iters"][i]].tolist(),
+                "t_diff": res["t_diff"][i, :res["iters"][i]].tolist(), "nn_launches": int(res["nn_launches"][i]), "device_ms": float(res["device_ms"][i]), "fused": bool(res["reserved"][i])}
+               for i in range(n)]
         if T_init is not None:
             for i, o in enumerate(out):
                 o["T_init"] = T_init[i].reshape(4, 4)

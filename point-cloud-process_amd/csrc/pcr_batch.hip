@@ -52,7 +52,7 @@ struct batch_target {         // per pair: what the plan kernel needs to write t
     double cell, hi[3];
     int levels;
     int pad;
-    double scale, inv_scale;
+    double scale, inv_scale, lin;
 };
 struct batch_plan {           // device: totals and prefix offsets written by the plan kernel
     unsigned long long used_cells, used_blocks;   // slots of the two pools in use
@@ -213,6 +213,8 @@ batch_plan_kernel(const unsigned int* __restrict__ counts, const batch_cloud* __
         pairs[t].nq = S.n;
         pairs[t].scale = tg[t].scale;
         pairs[t].inv_scale = tg[t].inv_scale;
+        pairs[t].lin = tg[t].lin;
+        pairs[t].inv_lin = 1.0 / tg[t].lin;
     }
 }
 
@@ -540,10 +542,11 @@ int batch_job::launch() {
         double cell_s = cell;
         if (cell_s < emax_s / 262144.0) cell_s = emax_s / 262144.0;
         S.inv = 1.0 / cell_s;
-        double sc = 0, isc = 0;
-        if (!pcr_pass_fixed_scale(T.lo, t_hi, S.n, params->max_d2, &sc, &isc)) { take[k] = 0; continue; }   // absurd extents: per-pair path (binary64 slabs)
+        double sc = 0, isc = 0, lin = 1.0;
+        if (!pcr_pass_fixed_scale(T.lo, t_hi, S.n, params->max_d2, &sc, &isc, &lin)) { take[k] = 0; continue; }   // absurd extents: per-pair path (binary64 slabs)
         tg[k].scale = sc;
         tg[k].inv_scale = isc;
+        tg[k].lin = lin;
         const int bt = pcr_morton_end_bit(T.lo, t_hi, T.inv), bs = pcr_morton_end_bit(S.lo, s_hi, S.inv);
         mbits = bt > mbits ? bt : mbits;
         mbits = bs > mbits ? bs : mbits;
@@ -557,7 +560,7 @@ int batch_job::launch() {
             cl[k].n = 0;       // (its slots stay, empty: no tile of it does anything; a shared scan is still brought over: n_copy)
             cl[m + k].n = 0;
             tg[k].levels = 0;
-            tg[k].cell = 1.0; tg[k].scale = tg[k].inv_scale = 1.0;
+            tg[k].cell = 1.0; tg[k].scale = tg[k].inv_scale = tg[k].lin = 1.0;
             for (int a = 0; a < 3; ++a) { tg[k].hi[a] = 0; cl[k].lo[a] = cl[m + k].lo[a] = 0; }
             cl[k].inv = cl[m + k].inv = 1.0;
         } else any = true;
@@ -776,8 +779,8 @@ int batch_job::end() {
         double T_cur[16], T_total[16];
         pcr::T_from_xform(S.x, T_cur);
         memcpy(T_total, S.T_total, sizeof(T_total));
-        if (!a.la.compat && S.status == PCR_OK && !S.converged && S.it == params->max_iter && params->max_iter > 0)
-            pcr::T_mul4(T_cur, T_total, T_total);   // icp_template.py:195-198: a non-converged last iteration still updates homo_mat_total
+        if (!a.la.compat && S.status == PCR_OK && !S.converged && S.it >= params->max_iter)
+            pcr::T_mul4(T_cur, T_total, T_total);   // icp_template.py:195-198: a non-converged last iteration still updates homo_mat_total (max_iter <= 0: by T0, as pcr_icp_finish)
         res->iters = S.it;
         res->status = S.status;
         res->n_assoc = S.n_assoc;
@@ -785,6 +788,7 @@ int batch_job::end() {
         res->mean_d2 = S.mean_d2;
         for (int i = 0; i < S.it && i < PCR_ICP_MAX_LOG; ++i) { res->r_diff[i] = S.r_diff[i]; res->t_diff[i] = S.t_diff[i]; }
         res->nn_launches = S.passes;
+        res->reserved = 1;   // "the fused batch stages produced this" (include/pcr.h)
         res->device_ms = icp_ms / (double)n_take;   // the pair's share of the sub-batch's loop
         memcpy(res->T_total, T_total, sizeof(T_total));
         memcpy(res->T, a.la.compat ? T_cur : T_total, sizeof(T_cur));

@@ -1073,6 +1073,7 @@ struct pass_args {
     unsigned long long* gate_lb;          // [nq] carried gate bounds (wtile_search), or null: feature off (PCR_PASS_GATE_LB=0, the batch)
     unsigned long long* gate_est;         // [nq] ... as established by the queue
     double scale, inv_scale;              // 2^F, 2^-F
+    double lin, inv_lin;                  // 2^(F1 - F), 2^-(F1 - F): the first moments (Sa, Sb) are kept at 2^F1 (pcr_pass_fixed_scale); 1 = same grid
     pcr_icp_dev_state* st;
     pcr_icp_loop_args la;
     unsigned int* tile_cost;              // [waves]: points every tile staged in the last pass (issue priority of this one)
@@ -1101,9 +1102,10 @@ __device__ static inline long long to_fixed(double v, double scale) {
 }
 
 // lanes 0..18 of the calling wave add one moment each (one vector atomic instruction); mk = this lane's moment
-__device__ static inline void acc_fixed_add(unsigned long long* __restrict__ acc, unsigned int set, int lane, double mk, double scale) {
+__device__ static inline bool mom_is_linear(int k) { return k >= 1 && k <= 6; }   // Sa[3], Sb[3] of the moment vector
+__device__ static inline void acc_fixed_add(unsigned long long* __restrict__ acc, unsigned int set, int lane, double mk, double scale, double lin) {
     if (lane < PCR_NMOM - 1 && mk != 0.0)
-        atomicAdd(acc + (size_t)(set % ACC_SETS) * PCR_NMOM + lane, (unsigned long long)to_fixed(mk, scale));   // two's complement
+        atomicAdd(acc + (size_t)(set % ACC_SETS) * PCR_NMOM + lane, (unsigned long long)to_fixed(mk, mom_is_linear(lane) ? scale * lin : scale));   // two's complement
 }
 
 __device__ static inline void acc_fixed_add_ll(unsigned long long* __restrict__ acc, unsigned int set, int lane, long long v) {
@@ -1167,7 +1169,7 @@ __device__ __forceinline__ static void pass_serve_item(const pcr_grid_view& gv, 
             for (int k = 0; k < PCR_NMOM - 1; ++k) L->xch[k] = m[k];
         }
         wave_sync();
-        acc_fixed_add(A.acc, qi, lane, lane < PCR_NMOM - 1 ? L->xch[lane] : 0.0, A.scale);
+        acc_fixed_add(A.acc, qi, lane, lane < PCR_NMOM - 1 ? L->xch[lane] : 0.0, A.scale, A.lin);
         wave_sync();
     }
     if (lane == 0) {
@@ -1217,7 +1219,7 @@ __device__ __forceinline__ static void pass_finish(const pcr_grid_view& gv, pass
     sum += __shfl(sum, lane + PCR_NMOM, 64) + __shfl(sum, lane + 2 * PCR_NMOM, 64);   // lanes 0..19: all three parts
     wave_sync();
     if (dbg && lane == 0) dbg[(1 << 19) - 3] = __builtin_amdgcn_s_memrealtime();
-    if (lane < PCR_NMOM) L->xch[lane] = (double)sum * A.inv_scale;
+    if (lane < PCR_NMOM) L->xch[lane] = (double)sum * (mom_is_linear(lane) ? A.inv_scale * A.inv_lin : A.inv_scale);
     if (lane < HEAD_WORDS) reinterpret_cast<unsigned long long*>(head)[lane] = hw;
     const bool gave_up = __builtin_amdgcn_readlane((int)(unsigned int)err_w, 63) != 0;
     wave_sync();
@@ -1319,7 +1321,7 @@ __device__ __forceinline__ static void publish_store(unsigned long long* items, 
 // integers are added (through the wave's LDS slice, then 19 atomics per wave): the totals do not depend on how queries are grouped
 // into tiles or queue items, or on any order.  A neighbour that came from the target records is the seed of the next pass's tile.
 __device__ __forceinline__ static void tile_fold_moments(pass_lds* L, int lane, const wt_state& S, const wt_pre& P, tile_nb& nb, const double origin[3], double max_d2,
-                                                wt_xyz* prev_xyz, const double& scale, unsigned long long* acc, unsigned int tile) {
+                                                wt_xyz* prev_xyz, const double& scale, const double& lin, unsigned long long* acc, unsigned int tile) {
     double m[PCR_NMOM];
 #pragma unroll
     for (int k = 0; k < PCR_NMOM; ++k) m[k] = 0.0;
@@ -1329,8 +1331,9 @@ __device__ __forceinline__ static void tile_fold_moments(pass_lds* L, int lane, 
         moments_add(m, origin, S.ax, S.ay, S.az, nb.b, max_d2, 1);
     }
     if (lane < WT_Q) {
+        const double scale1 = scale * lin;   // (a power of two; 1: the same grid, bit for bit)
 #pragma unroll
-        for (int k = 0; k < PCR_NMOM - 1; ++k) L->xll[lane * (PCR_NMOM - 1) + k] = to_fixed(m[k], scale);
+        for (int k = 0; k < PCR_NMOM - 1; ++k) L->xll[lane * (PCR_NMOM - 1) + k] = to_fixed(m[k], mom_is_linear(k) ? scale1 : scale);
     }
     wave_sync();
     long long tot = 0;
@@ -1456,7 +1459,7 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
             own = __hip_atomic_fetch_add(g_q, (1ull << (2 * Q_BITS)) | (all_started ? 1ull << Q_BITS : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (unres) publish_store<true>(A.items, A.cap, tg, slot_w, S, (unsigned int)S.qi);
     }
-    tile_fold_moments(L, lane, S, P, nb, gv.origin, max_d2, A.prev_xyz, A.scale, A.acc, tile);
+    tile_fold_moments(L, lane, S, P, nb, gv.origin, max_d2, A.prev_xyz, A.scale, A.lin, A.acc, tile);
     wave_sync();
     // ---- the reply of the done-add: this wave's first slot, and whether it was the last tile of its group
     {
@@ -1986,7 +1989,13 @@ pass_init_kernel(unsigned long long* __restrict__ zero_p, unsigned int zero_n, u
 
 // Fraction bits of the fixed-point moment accumulators.  Every moment is bounded by M = N * max(R^2, gate, 1), R = half diagonal
 // of the target box + gate radius: totals stay below 2^61, one correspondence's moments below 2^51 (to_fixed).
-bool pcr_pass_fixed_scale(const double lo[3], const double hi[3], long long nq, double max_d2, double* scale, double* inv_scale) {
+// The first moments (coordinate sums) are bounded by N * max(R, 1) only.  On the common grid each of them is off by up to 2^-(F+1) per
+// correspondence (uniform: 2^-(F+1) / sqrt(3) rms), their sums by sqrt(N) times that, and t = mean(b) - R mean(a) with them by about
+// e = 2^-(F+1) / sqrt(3 N): with few fraction bits (clouds tens of kilometres across) or few points that shows in the result (F = 20,
+// 1 000 points: 3e-8 in t measured).  Where e exceeds 1e-11 -- two orders below the project's 1e-9 -- they get a grid of their own,
+// F1 = min(61 - ex(N max(R, 1)), 51 - ex(max(R, 1))), *lin = 2^(F1 - F); everywhere else (every cloud of ordinary extent: e = 3e-12 at
+// 120 000 points in a scan's box, 2e-12 at 1 M) *lin = 1 and both grids are the same, bit for bit.
+bool pcr_pass_fixed_scale(const double lo[3], const double hi[3], long long nq, double max_d2, double* scale, double* inv_scale, double* lin) {
     double r2 = 0.0;
     for (int k = 0; k < 3; ++k) r2 += 0.25 * (hi[k] - lo[k]) * (hi[k] - lo[k]);
     const double R = sqrt(r2) + sqrt(max_d2);
@@ -1999,6 +2008,12 @@ bool pcr_pass_fixed_scale(const double lo[3], const double hi[3], long long nq, 
     if (!(M > 0) || !std::isfinite(M) || F < 20) return false;
     *scale = ldexp(1.0, F);
     *inv_scale = ldexp(1.0, -F);
+    int ex1 = 0, exq1 = 0;
+    frexp((double)nq * fmax(R, 1.0), &ex1);
+    frexp(fmax(R, 1.0), &exq1);
+    const int F1 = (61 - ex1 < 51 - exq1) ? 61 - ex1 : 51 - exq1;
+    const double e = ldexp(1.0, -(F + 1)) / sqrt(3.0 * (double)nq);
+    *lin = (e > 1e-11 && F1 > F) ? ldexp(1.0, F1 - F) : 1.0;
     return true;
 }
 
@@ -2027,9 +2042,9 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     // One-kernel pass (fixed-point accumulators): needs a gate (it bounds |a'| by the target's extent) and enough fraction
     // bits (absurd extents keep the binary64 slabs).  Every moment is bounded by M = N * max(R^2, gate, 1), R = half diagonal of
     // the target box + gate radius.
-    double sc_f = 0, sc_i = 0;
+    double sc_f = 0, sc_i = 0, sc_lin = 1.0;
     const bool fused = gated && nq <= PASS_MAX_NQ && getenv("PCR_ICP_NO_FUSED") == nullptr &&
-                       pcr_pass_fixed_scale(idx->lo, idx->hi, nq, params->max_d2, &sc_f, &sc_i);
+                       pcr_pass_fixed_scale(idx->lo, idx->hi, nq, params->max_d2, &sc_f, &sc_i, &sc_lin);
     grid_scratch sc(ctx);
     pcr_dev_block st_blk(ctx);
     if ((rc = grid_scratch_alloc(&sc, nq, false, !fused)) || (rc = sc.prev_xyz.alloc(24 * (size_t)nq))) return rc;
@@ -2055,6 +2070,8 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
         }
         pa.scale = sc_f;
         pa.inv_scale = sc_i;
+        pa.lin = sc_lin;
+        pa.inv_lin = 1.0 / sc_lin;
     }
     if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * PCR_NMOM * (size_t)grid)) || (rc = st_blk.alloc(sizeof(pcr_icp_dev_state)))) return rc;
     pcr_icp_dev_state* const d_st = st_blk.as<pcr_icp_dev_state>();
@@ -2244,7 +2261,7 @@ batch_pass_kernel(pcr_batch_pass_args B, int xcd_remap, unsigned int pcap, unsig
         const unsigned long long slot_w = publish_reserve(B.sync, um, unres, lane, g, n_groups, tg);
         if (unres) publish_store<false>(B.items, B.cap, tg, slot_w, S, (unsigned int)(q_off + (unsigned long long)S.qi));
     }
-    tile_fold_moments(L, lane, S, P, nb, bp->gv.origin, max_d2, prev_xyz, bp->scale, B.acc + (size_t)p * ACC_SETS * PCR_NMOM, tile);
+    tile_fold_moments(L, lane, S, P, nb, bp->gv.origin, max_d2, prev_xyz, bp->scale, bp->lin, B.acc + (size_t)p * ACC_SETS * PCR_NMOM, tile);
 }
 
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PCR_WT_WAVES, 8)))
@@ -2263,6 +2280,7 @@ batch_drain_kernel(pcr_batch_pass_args B) {
         A.acc = B.acc + (size_t)p * ACC_SETS * PCR_NMOM;
         A.prev_xyz = (wt_xyz*)B.prev_xyz;
         A.scale = bp->scale;
+        A.lin = bp->lin;
         pass_serve_item(bp->gv, L, lane, w, B.max_d2, A, B.res_pos, nullptr, w_i, 0ull);
     }
 }
@@ -2285,6 +2303,7 @@ batch_finish_kernel(pcr_batch_pass_args B, unsigned int pass_id) {
     A.st = st;
     A.la = B.la;
     A.inv_scale = bp->inv_scale;
+    A.inv_lin = bp->inv_lin;
     unsigned long long* const root = B.sync + (size_t)PASS_SYNC_STRIDE * PASS_GROUPS;   // (root + 16: the error word, never set here)
     pass_finish(bp->gv, L, lane, A, root, nullptr);
     wave_sync();

@@ -100,8 +100,9 @@ int pcr_icp_finish(pcr_ctx* ctx, pcr_cloud* source, const pcr_icp_params* params
     const bool compat = params->mode == PCR_ICP_COMPAT_MAIN;
     double T_cur[16];
     pcr::T_from_xform(st->x, T_cur);
-    if (!compat && st->status == PCR_OK && !st->converged && st->it == params->max_iter && params->max_iter > 0) {
-        // icp_template.py:195-198: a non-converged last iteration still updates src_points and homo_mat_total
+    if (!compat && st->status == PCR_OK && !st->converged && st->it >= params->max_iter) {
+        // icp_template.py:195-198: a non-converged last iteration still updates src_points and homo_mat_total.  With max_iter <= 0
+        // no pass ran and the transform pending is T0 itself: icp_template.py:146-152 applies the initial pose in front of the loop
         const int rc = pcr_cloud_transform(ctx, source, T_cur);
         if (rc) return rc;
         pcr::T_mul4(T_cur, st->T_total, st->T_total);

@@ -364,6 +364,7 @@ struct pcr_batch_pair {
     unsigned long long q_off;    // first source record = 32 x first wave tile
     long long nq;                // source points (<= slot size)
     double scale, inv_scale;     // 2^F, 2^-F of the pair's fixed-point moment accumulators
+    double lin, inv_lin;         // 2^(F1 - F) and its inverse: the grid of the first moments (pcr_pass_fixed_scale)
 };
 struct pcr_batch_pass_args {
     const pcr_batch_pair* pairs;       // device [n_pairs]
@@ -393,5 +394,5 @@ PCR_HIDDEN int pcr_grid_batch_pass(pcr_ctx* ctx, const pcr_batch_pass_args* a, u
 PCR_HIDDEN void pcr_grid_plan(const double lo[3], const double hi[3], long long n, double cell_in, double* cell_out, int* levels_out);
 PCR_HIDDEN int pcr_morton_end_bit(const double lo[3], const double hi[3], double inv);
 // fixed-point scale of the one-launch pass for a target box / source size / gate; false: cannot use the fused pass
-PCR_HIDDEN bool pcr_pass_fixed_scale(const double lo[3], const double hi[3], long long nq, double max_d2, double* scale, double* inv_scale);
+PCR_HIDDEN bool pcr_pass_fixed_scale(const double lo[3], const double hi[3], long long nq, double max_d2, double* scale, double* inv_scale, double* lin);
 

@@ -82,7 +82,10 @@ def test_empty_cloud_is_an_error(pcp):
 
 
 @pytest.mark.parametrize("kind", ["grid", "brute"])
-def test_fused_moments_match_oracle(pcp, oracle, syn, kind):
+def test_pass_moments_match_oracle(pcp, oracle, syn, kind):
+    """One association + accumulation pass (pcr_icp_moments) against the oracle's moments.  On the grid index this is the binary64 SLAB
+    path (pcr_grid_icp_pass: tile -> hard -> grid_accumulate_kernel), never the fixed-point accumulators of the one-kernel pass: those
+    are reachable through pcr_icp only and are held to the restated loop by tests/test_gpu_icp_loop.py."""
     src, tgt, Tt = syn.perturbed_pair(20000, seed=11)
     index = pcp.TargetIndex(tgt, kind=kind)
     m, origin, sum_d2 = index.moments(src, None, 5.0)
