@@ -568,6 +568,93 @@ PCR_API int pcr_kmeans_predict(pcr_ctx* ctx, const pcr_cloud* cloud, int k, int 
  * cloud this library makes satisfies; a row that no record carried would come back as NaN.                                     */
 PCR_API int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t* rows /* m caller rows */, int64_t m, double* xyz_out /* m*3 */);
 
+/* --------------------------------------------------------- spectral clustering
+ * class spetral_clustering (Cluster_KMeans_GMM/spectral_clustering.py:7-46, run by compare_cluster.py:105-107) on a device-resident
+ * cloud of n points.
+ *   graph (:17-30): the nnk nearest OTHER rows of every row (the exact k-NN of the grid index with k = nnk + 1, the row itself dropped
+ *     by id; ties by the lower row), joined to it in both directions: W is the union of the directed lists with one weight
+ *     w = 1 / dist per undirected edge, dist = sqrt((dx*dx + dy*dy) + dz*dz) as pcr_knn reports it.  W is kept as a CSR whose
+ *     columns ascend within a row; a row's length is not bounded by 2 nnk.  The degree d_i is the sum of row i's weights in column
+ *     order.  Two distinct rows at distance 0 (the reference's weight is infinite) end the call with PCR_E_SINGULAR,
+ *     bad_row = the lowest such caller row, nothing written.
+ *   eigenvectors (:32-39): the m = n_clusters smallest eigenpairs of the Laplacian, from the largest eigenvalues theta of a symmetric
+ *     operator B with spectrum in [-1, 1]:
+ *       normalized:     B = D^-1/2 W D^-1/2,          lambda = 1 - theta           (scale 1)
+ *       not normalized: B = I - (D - W) / d_max,      lambda = d_max (1 - theta)   (scale d_max = the largest degree)
+ *     Stated deviation: the reference calls LA.eig on the non-symmetric D^-1 L, which is similar to I - D^-1/2 W D^-1/2; the symmetric
+ *     form has real eigenpairs always, where LA.eig returns complex pairs on some inputs and the reference then raises.
+ *     n > 64: Chebyshev-filtered subspace iteration on a block of p = m + 8 vectors (binary64, row-major n x p).  Start: a hash of
+ *     (caller row, column) to (-1, 1), no RNG.  Outer iteration: the degree-20 Chebyshev filter that damps [-1, cut] (cut = the smallest
+ *     Ritz value of the previous iteration, 0 at first), the three-term recurrence fused into the sparse product; columns scaled to
+ *     unit norm and Cholesky-QR twice; Rayleigh-Ritz with a cyclic Jacobi solve of the p x p matrix; residuals
+ *     r_j = |B u_j - theta_j u_j|_2.  It stops with converged = 1 when r_j <= 2 tol for all j < m, else after max_iter iterations with
+ *     converged = 0 (eigenvalues, residuals and embedding of the last iterate are still returned).  A Cholesky pivot that is not
+ *     positive or not finite: PCR_E_SINGULAR with bad_row = -1.  spmm counts the sparse products (21 per outer iteration).
+ *     n <= 64: the dense n x n operator and the same Jacobi routine on the host (iters = 0, spmm = 0, converged = 1).
+ *     embedding column j (n x m, row-major, by caller row): normalized: D^-1/2 u_j (the eigenvector of D^-1 L), else u_j; scaled to
+ *     unit 2-norm; sign: the entry of largest magnitude is positive, the lowest caller row on ties.  Inside a repeated eigenvalue
+ *     only the span is defined, as in the reference.
+ *   K-Means (:43) on the rows of the embedding under the rules of pcr_kmeans_fit above (direct-form squared distances summed in
+ *     column order, the lowest cluster on ties, an empty cluster keeps its centre, stop on shift <= kmeans_tol, a final labelling
+ *     pass).  Seeds are rows of the embedding: the caller's seed_rows, or maximin from caller row 0 (seed j = the row with the largest
+ *     minimum squared distance to the seeds before it, the lowest row on ties).  Cluster j is the one seeded by seed j.  (The
+ *     reference calls scikit-learn's KMeans with k-means++ and restarts on the global RNG, which cannot be pinned.)
+ * Every sum runs in a fixed order without floating-point atomics: two calls on the same cloud give the same bits.  Rows and columns
+ * are kept in the Morton order of the index built for the k-NN; everything handed to the caller is by caller row.
+ * Limits, all checked before anything touches the device: 1 <= n_clusters <= PCR_SPECTRAL_MAX_K, 1 <= nnk <= PCR_SPECTRAL_MAX_NNK,
+ * max_iter >= 1, kmeans_max_iter >= 1, tol finite and > 0, kmeans_tol finite and >= 0, no NULL handle or required pointer: otherwise
+ * PCR_E_INVALID; then an empty cloud: PCR_E_EMPTY; then n < nnk + 2 (the reference raises IndexError), n < n_clusters, a seed row
+ * outside [0, n) or repeated: PCR_E_INVALID.                                                                                      */
+#define PCR_SPECTRAL_MAX_K 8
+#define PCR_SPECTRAL_MAX_NNK 15
+typedef struct pcr_spectral_params {
+    int32_t n_clusters;        /* -> 2 */
+    int32_t nnk;               /* -> 7 */
+    int32_t normalized;        /* -> 1 */
+    int32_t max_iter;          /* outer iterations of the eigensolver -> 200 */
+    int32_t kmeans_max_iter;   /* -> 300 */
+    int32_t reserved_i;
+    double tol;                /* on the residuals, absolute: r_j <= 2 tol -> 1e-8 */
+    double kmeans_tol;         /* -> 1e-4 */
+    double reserved[4];
+} pcr_spectral_params;
+typedef struct pcr_spectral_result {
+    int32_t iters;             /* outer iterations performed */
+    int32_t converged;
+    int32_t spmm;              /* sparse products performed */
+    int32_t max_degree;        /* the longest row of W */
+    int32_t bad_row;           /* PCR_E_SINGULAR from the graph: the lowest row with another row at distance 0; -1 otherwise */
+    int32_t kmeans_iters;
+    int32_t kmeans_converged;
+    int32_t n_empty;           /* clusters without points under the final centres */
+    int64_t n_edges;           /* undirected edges of W */
+    double eigenvalues[8];     /* lambda_j, j < n_clusters, ascending */
+    double residuals[8];       /* r_j of the operator B */
+    double next_eigenvalue;    /* lambda_{m+1} (a Ritz value of the guard block): the gap behind the last wanted one; NaN when n = m */
+    double inertia;            /* of the K-Means on the embedding, under the final centres */
+    double graph_ms;           /* HIP events: index, k-NN, CSR */
+    double solver_ms;          /* operator, subspace iteration, embedding */
+    double kmeans_ms;          /* seeds, Lloyd's loop, final pass */
+    double reserved[4];
+} pcr_spectral_result;
+PCR_API void pcr_spectral_default_params(pcr_spectral_params* p);   /* 2, 7, 1, 200, 300, 1e-8, 1e-4 */
+/* The graph alone, by caller row, in two passes like pcr_radius: with indices_out == NULL it fills indptr_out (n + 1 entries) only;
+ * with indices_out and weights_out (indptr_out[n] entries each, columns ascending) it fills all three.  bad_row_out (or NULL): -1, or
+ * the row of PCR_E_SINGULAR.                                                                                                      */
+PCR_API int pcr_knn_graph(pcr_ctx* ctx, const pcr_cloud* cloud, int nnk, int64_t* indptr_out /* n+1 */, int32_t* indices_out, double* weights_out,
+                          int32_t* bad_row_out);
+/* Graph and eigenvectors: embedding_out (n*m, by caller row); result's K-Means fields stay zero. */
+PCR_API int pcr_spectral_embed(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_spectral_params* params, double* embedding_out /* n*m */,
+                               pcr_spectral_result* result);
+/* spetral_clustering.fit: labels_out (int32[n] by caller row).  seed_rows (k caller rows) may be NULL: maximin.  embedding_out (n*m),
+ * centers_out (k*m, rows of the embedding space) and seed_rows_out (k, the seeds used) may be NULL.                               */
+PCR_API int pcr_spectral_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_spectral_params* params, const int64_t* seed_rows /* k or NULL */,
+                             int32_t* labels_out, double* embedding_out /* or NULL */, double* centers_out /* k*m or NULL */,
+                             int64_t* seed_rows_out /* k or NULL */, pcr_spectral_result* result);
+/* The cyclic Jacobi eigen-solve the kernels compile, on the host: A symmetric n x n row-major (not modified), 1 <= n <= 64 (else
+ * PCR_E_INVALID); eigvals_out (n) ascending, eigvecs_out (n x n row-major) column j = the unit eigenvector of eigvals_out[j].      */
+PCR_API int pcr_sym_eig_jacobi(int n, const double* A, double* eigvals_out, double* eigvecs_out);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

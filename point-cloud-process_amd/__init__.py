@@ -55,6 +55,7 @@ from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
+from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401
 from .batch import register_batch, shard_range  # noqa: F401
 from . import evaluate  # noqa: F401
 from .evaluate import evaluate_rt, get_P_diff, is_registration_successful  # noqa: F401

@@ -35,6 +35,8 @@ PCR_RMETRIC_GEODESIC = 1
 PCR_ICP_MAX_LOG = 256
 PCR_GMM_MAX_K = 32
 PCR_KMEANS_MAX_K = 32
+PCR_SPECTRAL_MAX_K = 8
+PCR_SPECTRAL_MAX_NNK = 15
 
 
 class IcpParams(C.Structure):
@@ -223,6 +225,42 @@ class KmeansResult(C.Structure):
     ]
 
 
+class SpectralParams(C.Structure):
+    _fields_ = [
+        ("n_clusters", C.c_int32),
+        ("nnk", C.c_int32),
+        ("normalized", C.c_int32),
+        ("max_iter", C.c_int32),
+        ("kmeans_max_iter", C.c_int32),
+        ("reserved_i", C.c_int32),
+        ("tol", C.c_double),
+        ("kmeans_tol", C.c_double),
+        ("reserved", C.c_double * 4),
+    ]
+
+
+class SpectralResult(C.Structure):
+    _fields_ = [
+        ("iters", C.c_int32),
+        ("converged", C.c_int32),
+        ("spmm", C.c_int32),
+        ("max_degree", C.c_int32),
+        ("bad_row", C.c_int32),
+        ("kmeans_iters", C.c_int32),
+        ("kmeans_converged", C.c_int32),
+        ("n_empty", C.c_int32),
+        ("n_edges", C.c_int64),
+        ("eigenvalues", C.c_double * 8),
+        ("residuals", C.c_double * 8),
+        ("next_eigenvalue", C.c_double),
+        ("inertia", C.c_double),
+        ("graph_ms", C.c_double),
+        ("solver_ms", C.c_double),
+        ("kmeans_ms", C.c_double),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -302,6 +340,11 @@ SIGNATURES = {
     "pcr_kmeans_step": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _dp, _lp, _dp, _dp, _dp]),
     "pcr_kmeans_predict": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _dp, _ip, _lp, _dp]),
     "pcr_cloud_download_rows": (C.c_int, [_vp, _vp, _lp, C.c_int64, _dp]),
+    "pcr_spectral_default_params": (None, [C.POINTER(SpectralParams)]),
+    "pcr_knn_graph": (C.c_int, [_vp, _vp, C.c_int, _lp, _ip, _dp, _ip]),
+    "pcr_spectral_embed": (C.c_int, [_vp, _vp, C.POINTER(SpectralParams), _dp, C.POINTER(SpectralResult)]),
+    "pcr_spectral_fit": (C.c_int, [_vp, _vp, C.POINTER(SpectralParams), _lp, _ip, _dp, _dp, _lp, C.POINTER(SpectralResult)]),
+    "pcr_sym_eig_jacobi": (C.c_int, [C.c_int, _dp, _dp, _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),

@@ -244,6 +244,7 @@ enum pcr_cw {
     PCR_CW_BRUTE_FLAGS,     // pcr_brute: [0] flagged queries, [1] those of the last call
     PCR_CW_ISS_CAND,        // pcr_iss: candidates
     PCR_CW_KNN_LEFT,        // pcr_knn: queries left by [0] stage 2, [1] the full block scan, [2] stage 1
+    PCR_CW_SPECTRAL_TICKET, // pcr_spectral
     PCR_CW_USERS
 };
 struct pcr_cw_span { int first, words; };
@@ -261,6 +262,7 @@ constexpr pcr_cw_span PCR_CW_SPAN[PCR_CW_USERS] = {
     {120, 2},   // BRUTE_FLAGS    120..121
     {124, 1},   // ISS_CAND
     {125, 3},   // KNN_LEFT       125..127
+    {136, 1},   // SPECTRAL_TICKET
 };
 constexpr bool pcr_cw_disjoint() {
     int end = 0;
@@ -350,6 +352,9 @@ PCR_HIDDEN int pcr_voxel_downsample_scans(pcr_ctx* ctx, const float* d_xyz, int6
 constexpr size_t PCR_SMALL_D2H_BYTES = 16384;
 PCR_HIDDEN int pcr_d2h_small(pcr_ctx* ctx, void* host_dst, const void* dev_src, size_t bytes);
 PCR_HIDDEN int pcr_wait_flag(pcr_ctx* ctx, double* flag_us);
+// pcr_knn between its upload and its download (pcr_knn.hip): q queries (3 doubles each) resident at d_q, results left at d_idx / d_dist
+// [i * k, ...); enqueued on the context's stream, any q and k
+PCR_HIDDEN int pcr_knn_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t q, int k, int* d_idx, double* d_dist);
 PCR_HIDDEN int pcr_d2h_small_enqueue(pcr_ctx* ctx, void* mapped_host_dst, const void* dev_src, size_t bytes);
 // whole ICP loop on the device (grid index); fills res like the host loop of pcr_icp
 PCR_HIDDEN int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_icp_params* params, const double T0[16],

@@ -634,6 +634,62 @@ static int small_block(pcr_ctx* ctx, size_t bytes, char** host, char** dev) {
     return PCR_OK;
 }
 
+// The search of pcr_knn behind its upload and in front of its download: q queries (3 doubles each) resident at d_q, the k results of
+// query i left at d_idx / d_dist [i * k, ...).  Enqueued on the context's stream; the batched path reads its three list lengths back.
+int pcr_knn_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t q, int k, int* d_idx, double* d_dist) {
+    int rc;
+    pcr_dev_block b_redo(ctx);
+    if (k <= 16 && q >= 256) {
+        // Batched path, three stages, each handing what it cannot prove to the next through a list:
+        //   1. the lane-per-query scan at the finest level(s) only -- a query's own 27 cells: where it is fast and proves the easy majority;
+        //   2. ONE QUERY PER WAVE for what it leaves: all 64 lanes scan the query's own box -- its cells and a ring, then the ball its
+        //      k-th distance so far defines, or rings of 4, 16, 64 ... cells while it lacks k points (knn_tile_kernel);
+        //   3. the lane-per-query scan at every level and the wave-per-query descent for what is left (clamped coordinates).
+        unsigned int* d_cnt_a = pcr_counter(ctx, PCR_CW_KNN_LEFT);      // queries stage 2 left
+        unsigned int* d_cnt_b = pcr_counter(ctx, PCR_CW_KNN_LEFT, 1);   // queries the full block scan left (-> descent)
+        unsigned int* d_cnt_d = pcr_counter(ctx, PCR_CW_KNN_LEFT, 2);   // queries stage 1 left
+        pcr_dev_block b_redo2(ctx), b_redo4(ctx), b_kth(ctx);
+        if ((rc = b_redo.alloc(sizeof(int) * q)) || (rc = b_redo2.alloc(sizeof(int) * q)) || (rc = b_redo4.alloc(sizeof(int) * q)) || (rc = b_kth.alloc(sizeof(double) * q))) return rc;
+        double* d_kth = b_kth.as<double>();   // stage 1 hands the k-th distance it found to stage 2 as the first ball
+        int *d_redo_a = b_redo.as<int>(), *d_redo_b = b_redo2.as<int>(), *d_redo_d = b_redo4.as<int>();
+        PCR_HIP(ctx, hipMemsetAsync(d_cnt_a, 0, 3 * sizeof(unsigned int), ctx->stream));
+        const unsigned gb = (unsigned)((q + 255) / 256);
+        const int lv_first = k > 8 ? 1 : 0;   // (k = 16, a scan against itself: 44 000 of 120 000 queries are left at level 0)
+        unsigned gw = (unsigned)((q + 3) / 4);
+        if (gw > 8u * (unsigned)ctx->cu_count) gw = 8u * (unsigned)ctx->cu_count;   // (a fixed grid strides over the list: its length is only known on the device)
+        if (k <= 8) {
+            hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
+                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
+            hipLaunchKernelGGL((knn_tile_kernel<8, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
+                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
+        } else {
+            hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
+                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
+            hipLaunchKernelGGL((knn_tile_kernel<16, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
+                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
+        }
+        const int* todo = d_redo_a;
+        if (k <= 8)
+            hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
+                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
+        else
+            hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
+                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
+        unsigned int n_redo[3] = {0, 0, 0};
+        { const int rc_n = pcr_d2h_small(ctx, n_redo, d_cnt_a, 3 * sizeof(unsigned int)); if (rc_n) return rc_n; }   // (synchronises; no copy engine)
+        static const bool dbg = getenv("PCR_KNN_DEBUG") != nullptr;
+        if (dbg) fprintf(stderr, "pcr_knn: %lld queries, k = %d: %u left by the first scan, %u by the wave-per-query boxes, %u to the descent\n", (long long)q, k, n_redo[2], n_redo[0], n_redo[1]);
+        if (n_redo[1])
+            hipLaunchKernelGGL(knn_kernel, dim3((n_redo[1] + 3) / 4), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, (const int*)d_redo_b,
+                               (const unsigned int*)d_cnt_b);
+    } else {
+        hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, (const int*)nullptr,
+                           (const unsigned int*)nullptr);
+    }
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
 extern "C" {
 
 int pcr_radius_small(pcr_ctx* ctx, const pcr_index* index, const double* queries, int q, double radius, int64_t cap, int64_t* counts_out,
@@ -708,62 +764,12 @@ int pcr_knn(pcr_ctx* ctx, const pcr_index* index, const double* queries, int64_t
         memcpy(dist_out, h + o_d, 8 * (size_t)q * k);
         return PCR_OK;
     }
-    pcr_dev_block b_q(ctx), b_idx(ctx), b_dist(ctx), b_redo(ctx);   // (back to the arena on every return path)
+    pcr_dev_block b_q(ctx), b_idx(ctx), b_dist(ctx);   // (back to the arena on every return path)
     if ((rc = b_q.alloc(sizeof(double) * 3 * q)) || (rc = b_idx.alloc(sizeof(int) * q * k)) || (rc = b_dist.alloc(sizeof(double) * q * k))) return rc;
-    const double* d_q = b_q.as<const double>();
-    int* d_idx = b_idx.as<int>();
-    double* d_dist = b_dist.as<double>();
     PCR_HIP(ctx, hipMemcpyAsync(b_q.p, queries, sizeof(double) * 3 * q, hipMemcpyHostToDevice, ctx->stream));
-    if (k <= 16 && q >= 256) {
-        // Batched path, three stages, each handing what it cannot prove to the next through a list:
-        //   1. the lane-per-query scan at the finest level(s) only -- a query's own 27 cells: where it is fast and proves the easy majority;
-        //   2. ONE QUERY PER WAVE for what it leaves: all 64 lanes scan the query's own box -- its cells and a ring, then the ball its
-        //      k-th distance so far defines, or rings of 4, 16, 64 ... cells while it lacks k points (knn_tile_kernel);
-        //   3. the lane-per-query scan at every level and the wave-per-query descent for what is left (clamped coordinates).
-        unsigned int* d_cnt_a = pcr_counter(ctx, PCR_CW_KNN_LEFT);      // queries stage 2 left
-        unsigned int* d_cnt_b = pcr_counter(ctx, PCR_CW_KNN_LEFT, 1);   // queries the full block scan left (-> descent)
-        unsigned int* d_cnt_d = pcr_counter(ctx, PCR_CW_KNN_LEFT, 2);   // queries stage 1 left
-        pcr_dev_block b_redo2(ctx), b_redo4(ctx), b_kth(ctx);
-        if ((rc = b_redo.alloc(sizeof(int) * q)) || (rc = b_redo2.alloc(sizeof(int) * q)) || (rc = b_redo4.alloc(sizeof(int) * q)) || (rc = b_kth.alloc(sizeof(double) * q))) return rc;
-        double* d_kth = b_kth.as<double>();   // stage 1 hands the k-th distance it found to stage 2 as the first ball
-        int *d_redo_a = b_redo.as<int>(), *d_redo_b = b_redo2.as<int>(), *d_redo_d = b_redo4.as<int>();
-        PCR_HIP(ctx, hipMemsetAsync(d_cnt_a, 0, 3 * sizeof(unsigned int), ctx->stream));
-        const unsigned gb = (unsigned)((q + 255) / 256);
-        const int lv_first = k > 8 ? 1 : 0;   // (k = 16, a scan against itself: 44 000 of 120 000 queries are left at level 0)
-        unsigned gw = (unsigned)((q + 3) / 4);
-        if (gw > 8u * (unsigned)ctx->cu_count) gw = 8u * (unsigned)ctx->cu_count;   // (a fixed grid strides over the list: its length is only known on the device)
-        if (k <= 8) {
-            hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
-                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
-            hipLaunchKernelGGL((knn_tile_kernel<8, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
-                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
-        } else {
-            hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_d, d_cnt_d,
-                               (const int*)nullptr, (const unsigned int*)nullptr, lv_first, d_kth);
-            hipLaunchKernelGGL((knn_tile_kernel<16, 64, 7, 512>), dim3(gw), dim3(256), 0, ctx->stream, index->view, d_q, (const unsigned int*)d_redo_d, (long long)q,
-                               (const unsigned int*)d_cnt_d, k, d_idx, d_dist, d_redo_a, d_cnt_a, (const double*)d_kth);
-        }
-        const int* todo = d_redo_a;
-        if (k <= 8)
-            hipLaunchKernelGGL(knn_block_kernel<8>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
-                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
-        else
-            hipLaunchKernelGGL(knn_block_kernel<16>, dim3(gb), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_redo_b, d_cnt_b, todo,
-                               (const unsigned int*)d_cnt_a, KNN_LV, (double*)nullptr);
-        unsigned int n_redo[3] = {0, 0, 0};
-        { const int rc_n = pcr_d2h_small(ctx, n_redo, d_cnt_a, 3 * sizeof(unsigned int)); if (rc_n) return rc_n; }   // (synchronises; no copy engine)
-        static const bool dbg = getenv("PCR_KNN_DEBUG") != nullptr;
-        if (dbg) fprintf(stderr, "pcr_knn: %lld queries, k = %d: %u left by the first scan, %u by the wave-per-query boxes, %u to the descent\n", (long long)q, k, n_redo[2], n_redo[0], n_redo[1]);
-        if (n_redo[1])
-            hipLaunchKernelGGL(knn_kernel, dim3((n_redo[1] + 3) / 4), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, (const int*)d_redo_b,
-                               (const unsigned int*)d_cnt_b);
-    } else {
-        hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, (const int*)nullptr,
-                           (const unsigned int*)nullptr);
-    }
-    PCR_HIP(ctx, hipGetLastError());
-    if ((rc = pcr_d2h_staged(ctx, idx_out, d_idx, sizeof(int) * (size_t)q * k))) return rc;
-    if ((rc = pcr_d2h_staged(ctx, dist_out, d_dist, sizeof(double) * (size_t)q * k))) return rc;
+    if ((rc = pcr_knn_dev(ctx, index, b_q.as<const double>(), q, k, b_idx.as<int>(), b_dist.as<double>()))) return rc;
+    if ((rc = pcr_d2h_staged(ctx, idx_out, b_idx.p, sizeof(int) * (size_t)q * k))) return rc;
+    if ((rc = pcr_d2h_staged(ctx, dist_out, b_dist.p, sizeof(double) * (size_t)q * k))) return rc;
     PCR_HIP(ctx, pcr_sync(ctx->stream));
     return PCR_OK;
 }
