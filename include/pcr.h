@@ -655,6 +655,51 @@ PCR_API int pcr_spectral_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_spe
  * PCR_E_INVALID); eigvals_out (n) ascending, eigvecs_out (n x n row-major) column j = the unit eigenvector of eigvals_out[j].      */
 PCR_API int pcr_sym_eig_jacobi(int n, const double* A, double* eigvals_out, double* eigvecs_out);
 
+/* ------------------------------------------- PointNet++ set-abstraction ops
+ * The op library of the reference's classifier (Final_Project/pointnet2_ops_lib/pointnet2_ops/pointnet2_utils.py: furthest_point_sample
+ * :65, gather_operation :101, three_nn :136, three_interpolate :191, grouping_operation :240, ball_query :276), whose native half
+ * exists only as CUDA.  Unlike the rest of this header these functions work on the CALLER'S device memory:
+ *   - every array is a device pointer on the current device, C-contiguous, binary32 data and int32 indices, laid out as the
+ *     reference lays them out (shapes are given beside each parameter);
+ *   - `stream` is a hipStream_t (NULL: the null stream); the kernels are enqueued there and the call returns at once;
+ *   - no pcr_ctx, no allocation, no host synchronisation; workspaces are the caller's;
+ *   - PCR_OK, PCR_E_INVALID (a negative size, no input points or a NULL pointer where the output is not empty, a radius that is
+ *     not finite, more than 2^31 - 1 blocks) or PCR_E_HIP (the launch failed).  b == 0 or any other size that makes the output
+ *     empty: PCR_OK, nothing is launched.
+ * Arithmetic is binary32 without contraction, in the order written below, so a NumPy float32 restatement gives the same bits.
+ * Inputs must be finite and every entry of an index array must lie inside the array it addresses; neither is validated.
+ *
+ * Furthest point sampling, per cloud of n points, m picks:
+ *   eligible(k): ((x*x + y*y) + z*z of point k, binary32), widened to binary64, > 1e-3.  A point that is not eligible is never
+ *                updated and never chosen (padding rows at the origin).
+ *   temp[k] = 1e10f.  pick 0 = index 0, whether eligible or not.
+ *   pick j >= 1: p = the point of pick j-1; for every eligible k: d = ((dx*dx) + (dy*dy)) + (dz*dz) with dx = x_k - x_p, ...;
+ *                temp[k] = min(d, temp[k]); the pick is the eligible k of the largest temp[k], the LOWEST k among equals;
+ *                no eligible point at all: the pick is 0.
+ *   m > n is legal (picks repeat).  The tie rule is a rule of its own: in the reference the winner among equal distances depends on
+ *   how many threads its block happens to have, which no caller can rely on.
+ *   temp is a workspace of b*n floats; its contents afterwards are unspecified.
+ * Ball query: r = radius as binary32, r2 = r*r in binary32; d2 = ((dx*dx) + (dy*dy)) + (dz*dz).  A centre's row holds, in increasing
+ *   index order, the first nsample points with d2 < r2 (strictly); a centre with fewer hits fills the rest of its row with its
+ *   first hit; a centre without a hit gets a row of zeros.
+ * three_nn: for every unknown point the three smallest d (same form) over the known points, ascending, kept by insertion with a
+ *   strict <: of equal distances the earlier index stays ahead.  m < 3: the empty slots report +inf and index 0.  dist2_out holds
+ *   SQUARED distances.
+ * three_interpolate: out[b,c,i] = (p[idx0]*w0 + p[idx1]*w1) + p[idx2]*w2 with p = points[b,c,:], idx and w from row (b,i).
+ * gather_points: out[b,c,j] = points[b,c,idx[b,j]].  group_points: out[b,c,j,s] = points[b,c,idx[b,j,s]].                       */
+PCR_API int pcr_pn2_furthest_point_sampling(void* stream, int b, int n, int m, const float* xyz /* b,n,3 */, float* temp /* b,n workspace */,
+                                            int32_t* idx_out /* b,m */);
+PCR_API int pcr_pn2_ball_query(void* stream, int b, int n, int m, float radius, int nsample, const float* new_xyz /* b,m,3 */,
+                               const float* xyz /* b,n,3 */, int32_t* idx_out /* b,m,nsample */);
+PCR_API int pcr_pn2_three_nn(void* stream, int b, int n, int m, const float* unknown /* b,n,3 */, const float* known /* b,m,3 */,
+                             float* dist2_out /* b,n,3 */, int32_t* idx_out /* b,n,3 */);
+PCR_API int pcr_pn2_three_interpolate(void* stream, int b, int c, int m, int n, const float* points /* b,c,m */, const int32_t* idx /* b,n,3 */,
+                                      const float* weight /* b,n,3 */, float* out /* b,c,n */);
+PCR_API int pcr_pn2_gather_points(void* stream, int b, int c, int n, int npoints, const float* points /* b,c,n */, const int32_t* idx /* b,npoints */,
+                                  float* out /* b,c,npoints */);
+PCR_API int pcr_pn2_group_points(void* stream, int b, int c, int n, int npoints, int nsample, const float* points /* b,c,n */,
+                                 const int32_t* idx /* b,npoints,nsample */, float* out /* b,c,npoints,nsample */);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

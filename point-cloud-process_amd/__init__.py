@@ -62,3 +62,16 @@ from .evaluate import evaluate_rt, get_P_diff, is_registration_successful  # noq
 from .drivers import read_pair_list, run_registration  # noqa: F401
 
 __version__ = "0.1.0"
+
+# The PointNet++ ops are torch modules and autograd functions: they come in on first use, so that importing the package does not
+# import torch (see PCR_NO_TORCH_PRELOAD in _lib.py).
+_POINTNET2_EXPORTS = ("pointnet2_ops", "pointnet2_utils", "pointnet2_modules", "furthest_point_sample_np")
+
+
+def __getattr__(name):
+    if name in _POINTNET2_EXPORTS:
+        import importlib
+
+        ops = importlib.import_module(__name__ + ".pointnet2_ops")
+        return ops if name == "pointnet2_ops" else getattr(ops, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

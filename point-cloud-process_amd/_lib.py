@@ -345,6 +345,13 @@ SIGNATURES = {
     "pcr_spectral_embed": (C.c_int, [_vp, _vp, C.POINTER(SpectralParams), _dp, C.POINTER(SpectralResult)]),
     "pcr_spectral_fit": (C.c_int, [_vp, _vp, C.POINTER(SpectralParams), _lp, _ip, _dp, _dp, _lp, C.POINTER(SpectralResult)]),
     "pcr_sym_eig_jacobi": (C.c_int, [C.c_int, _dp, _dp, _dp]),
+    # PointNet++ ops: (stream, sizes..., device pointers...) -- addresses of the caller's device tensors, hence plain void*
+    "pcr_pn2_furthest_point_sampling": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "pcr_pn2_ball_query": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
+    "pcr_pn2_three_nn": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "pcr_pn2_three_interpolate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "pcr_pn2_gather_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "pcr_pn2_group_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),

@@ -58,6 +58,28 @@ __device__ static inline int wave_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x143, 0xc, 0xf, false));
     return __builtin_amdgcn_readlane(v, 63);
 }
+// unsigned 64-bit maximum on the same network (lanes without a source keep their own value).  row_max_u64: the first four steps, the
+// maximum of each row of 16 lanes in its lane 15; wave_max_u64: the maximum of the wave, in every lane
+template <int CTRL, int ROW_MASK>
+__device__ static inline unsigned long long dpp_max_u64(unsigned long long v) {
+    const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp((int)(unsigned int)v, (int)(unsigned int)v, CTRL, ROW_MASK, 0xf, false);
+    const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp((int)(unsigned int)(v >> 32), (int)(unsigned int)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    return o > v ? o : v;
+}
+__device__ static inline unsigned long long row_max_u64(unsigned long long v) {
+    v = dpp_max_u64<0x111, 0xf>(v);
+    v = dpp_max_u64<0x112, 0xf>(v);
+    v = dpp_max_u64<0x114, 0xf>(v);
+    v = dpp_max_u64<0x118, 0xf>(v);
+    return v;
+}
+__device__ static inline unsigned long long wave_max_u64(unsigned long long v) {
+    v = row_max_u64(v);
+    v = dpp_max_u64<0x142, 0xa>(v);
+    v = dpp_max_u64<0x143, 0xc>(v);
+    return ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), 63) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, 63);
+}
 __device__ static inline double vmin(double a, double b) {  // plain v_min_f64 (fmin() adds two canonicalising v_max)
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));

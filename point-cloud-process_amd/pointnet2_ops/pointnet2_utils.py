@@ -1,0 +1,282 @@
+"""The reference's ``pointnet2_ops.pointnet2_utils`` (Final_Project/pointnet2_ops_lib/pointnet2_ops/pointnet2_utils.py) on the MI355X:
+the same names and signatures, torch tensors on the device in and out, the six forward ops as HIP kernels behind the C ABI
+(include/pcr.h, "PointNet++ set-abstraction ops") launched on torch's current stream with the tensors' own addresses.
+
+Every argument is checked before anything is launched and a bad one raises ValueError: dtype (float32 data, int32 indices), rank,
+contiguity, matching batch sizes, and that the tensors live on a GPU.  There is no host path.
+
+The three gradients (gather, group, interpolate) are composed from torch's ``scatter_add_`` on the device, so training works; their
+summation order is torch's (floating-point atomics), not a fixed one.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+from torch.autograd import Function
+
+from .. import _lib
+
+_INT_MAX = 2**31 - 1
+
+
+def _check(*specs, device=True):
+    """specs: (tensor, name, dtype, shape) with shape entries None (free), an int (required) or a letter (equal among the specs)."""
+    named = {}
+    for t, name, dtype, shape in specs:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a torch.Tensor, not {type(t).__name__}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must have dtype {dtype}, not {t.dtype}")
+        if t.dim() != len(shape):
+            raise ValueError(f"{name} must have rank {len(shape)}, not {t.dim()}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    for t, name, dtype, shape in specs:
+        for axis, want in enumerate(shape):
+            have = t.shape[axis]
+            if have > _INT_MAX:
+                raise ValueError(f"{name}: axis {axis} has {have} entries, more than an int32 index reaches")
+            if isinstance(want, int) and have != want:
+                raise ValueError(f"{name} must have {want} entries along axis {axis}, not {have}")
+            if isinstance(want, str):
+                other = named.setdefault(want, (have, name, axis))
+                if other[0] != have:
+                    what = "batch sizes" if want == "B" else "sizes"
+                    raise ValueError(f"mismatched {what}: {other[1]} has {other[0]} along axis {other[2]}, {name} has {have} along axis {axis}")
+    if device:
+        first = specs[0][0]
+        for t, name, dtype, shape in specs:
+            if t.device.type != "cuda":
+                raise ValueError(f"{name} must be on the GPU (it is on {t.device}): these ops have no host path")
+            if t.device != first.device:
+                raise ValueError(f"{name} is on {t.device}, {specs[0][1]} on {first.device}")
+
+
+def _count(value, name, least=0):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least or value > _INT_MAX:
+        raise ValueError(f"{name} must be an integer in [{least}, 2^31), not {value!r}")
+    return int(value)
+
+
+def _launch(anchor, fn_name, *args):
+    """One C-ABI call on the current stream of `anchor`'s device."""
+    with torch.cuda.device(anchor.device):
+        fn = getattr(_lib.lib(), fn_name)
+        _lib.check(fn(torch.cuda.current_stream().cuda_stream, *args))
+
+
+f32, i32 = torch.float32, torch.int32
+
+
+class FurthestPointSampling(Function):
+    @staticmethod
+    def forward(ctx, xyz, npoint):
+        """xyz (B, N, 3) float32 -> (B, npoint) int32: iterative furthest point sampling from index 0; of equally far points the
+        lowest index wins, points with |p|^2 <= 1e-3 are padding and never chosen (include/pcr.h)."""
+        _check((xyz, "xyz", f32, ("B", None, 3)))
+        npoint = _count(npoint, "npoint")
+        B, N, _ = xyz.shape
+        if N == 0 and B and npoint:
+            raise ValueError("xyz has no points to sample from")
+        out = torch.empty((B, npoint), dtype=i32, device=xyz.device)
+        temp = torch.empty((B, N), dtype=f32, device=xyz.device)
+        _launch(xyz, "pcr_pn2_furthest_point_sampling", B, N, npoint, xyz.data_ptr(), temp.data_ptr(), out.data_ptr())
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ()
+
+
+furthest_point_sample = FurthestPointSampling.apply
+
+
+def _scatter_rows(grad_cols, idx_cols, n):
+    """sum of grad_cols (B, C, K) into (B, C, n) at idx_cols (B, K): the transpose of a gather along the last axis."""
+    B, C, K = grad_cols.shape
+    out = torch.zeros((B, C, n), dtype=grad_cols.dtype, device=grad_cols.device)
+    return out.scatter_add_(2, idx_cols.to(torch.int64).view(B, 1, K).expand(B, C, K), grad_cols)
+
+
+class GatherOperation(Function):
+    @staticmethod
+    def forward(ctx, features, idx):
+        """features (B, C, N) float32, idx (B, npoint) int32 -> (B, C, npoint): out[b, c, j] = features[b, c, idx[b, j]]."""
+        _check((features, "features", f32, ("B", None, None)), (idx, "idx", i32, ("B", None)))
+        B, C, N = features.shape
+        npoint = idx.shape[1]
+        if N == 0 and B and C and npoint:
+            raise ValueError("features has no points to gather from")
+        out = torch.empty((B, C, npoint), dtype=f32, device=features.device)
+        _launch(features, "pcr_pn2_gather_points", B, C, N, npoint, features.data_ptr(), idx.data_ptr(), out.data_ptr())
+        ctx.save_for_backward(idx)
+        ctx.n = N
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        return _scatter_rows(grad_out.contiguous(), idx, ctx.n), None
+
+
+gather_operation = GatherOperation.apply
+
+
+def _three_nn_dist2(unknown, known):
+    """(squared distances, indices) of the three nearest known points of every unknown point, as the kernel leaves them."""
+    _check((unknown, "unknown", f32, ("B", None, 3)), (known, "known", f32, ("B", None, 3)))
+    B, n, _ = unknown.shape
+    m = known.shape[1]
+    if m == 0 and B and n:
+        raise ValueError("known has no points")
+    dist2 = torch.empty((B, n, 3), dtype=f32, device=unknown.device)
+    idx = torch.empty((B, n, 3), dtype=i32, device=unknown.device)
+    _launch(unknown, "pcr_pn2_three_nn", B, n, m, unknown.data_ptr(), known.data_ptr(), dist2.data_ptr(), idx.data_ptr())
+    return dist2, idx
+
+
+class ThreeNN(Function):
+    @staticmethod
+    def forward(ctx, unknown, known):
+        """unknown (B, n, 3), known (B, m, 3) -> dist (B, n, 3) float32 (Euclidean, ascending) and idx (B, n, 3) int32; fewer than
+        three known points: the empty slots are +inf and index 0."""
+        dist2, idx = _three_nn_dist2(unknown, known)
+        dist = torch.sqrt(dist2)
+        ctx.mark_non_differentiable(dist, idx)
+        return dist, idx
+
+    @staticmethod
+    def backward(ctx, grad_dist, grad_idx):
+        return ()
+
+
+three_nn = ThreeNN.apply
+
+
+class ThreeInterpolate(Function):
+    @staticmethod
+    def forward(ctx, features, idx, weight):
+        """features (B, c, m), idx (B, n, 3) int32, weight (B, n, 3) -> (B, c, n): the weighted sum of three columns of features."""
+        _check((features, "features", f32, ("B", None, None)), (idx, "idx", i32, ("B", "n", 3)), (weight, "weight", f32, ("B", "n", 3)))
+        B, c, m = features.shape
+        n = idx.shape[1]
+        if m == 0 and B and c and n:
+            raise ValueError("features has no points to interpolate from")
+        out = torch.empty((B, c, n), dtype=f32, device=features.device)
+        _launch(features, "pcr_pn2_three_interpolate", B, c, m, n, features.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
+        ctx.save_for_backward(idx, weight)
+        ctx.m = m
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        """Gradient of the features only (as in the reference, the weights get none)."""
+        idx, weight = ctx.saved_tensors
+        B, c, n = grad_out.shape
+        terms = (grad_out.unsqueeze(-1) * weight.unsqueeze(1)).reshape(B, c, 3 * n)
+        return _scatter_rows(terms, idx.reshape(B, 3 * n), ctx.m), None, None
+
+
+three_interpolate = ThreeInterpolate.apply
+
+
+class GroupingOperation(Function):
+    @staticmethod
+    def forward(ctx, features, idx):
+        """features (B, C, N), idx (B, npoint, nsample) int32 -> (B, C, npoint, nsample): out[b, c, j, s] = features[b, c, idx[b, j, s]]."""
+        _check((features, "features", f32, ("B", None, None)), (idx, "idx", i32, ("B", None, None)))
+        B, C, N = features.shape
+        _, npoint, nsample = idx.shape
+        if N == 0 and B and C and npoint and nsample:
+            raise ValueError("features has no points to group")
+        out = torch.empty((B, C, npoint, nsample), dtype=f32, device=features.device)
+        _launch(features, "pcr_pn2_group_points", B, C, N, npoint, nsample, features.data_ptr(), idx.data_ptr(), out.data_ptr())
+        ctx.save_for_backward(idx)
+        ctx.n = N
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (idx,) = ctx.saved_tensors
+        B, C = grad_out.shape[:2]
+        return _scatter_rows(grad_out.reshape(B, C, -1), idx.reshape(B, -1), ctx.n), None
+
+
+grouping_operation = GroupingOperation.apply
+
+
+class BallQuery(Function):
+    @staticmethod
+    def forward(ctx, radius, nsample, xyz, new_xyz):
+        """xyz (B, N, 3), new_xyz (B, npoint, 3) -> (B, npoint, nsample) int32: per centre the first nsample points, by index, strictly
+        inside the ball; short rows are filled with their first hit, rows without a hit with 0."""
+        _check((xyz, "xyz", f32, ("B", None, 3)), (new_xyz, "new_xyz", f32, ("B", None, 3)))
+        nsample = _count(nsample, "nsample")
+        radius = float(radius)
+        if not np.isfinite(np.float32(radius)):
+            raise ValueError(f"radius must be finite as a float32, not {radius!r}")
+        B, N, _ = xyz.shape
+        npoint = new_xyz.shape[1]
+        if N == 0 and B and npoint and nsample:
+            raise ValueError("xyz has no points to query")
+        out = torch.empty((B, npoint, nsample), dtype=i32, device=xyz.device)
+        _launch(xyz, "pcr_pn2_ball_query", B, N, npoint, radius, nsample, new_xyz.data_ptr(), xyz.data_ptr(), out.data_ptr())
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return ()
+
+
+ball_query = BallQuery.apply
+
+
+class QueryAndGroup(nn.Module):
+    """Ball query around every centre, then the neighbours' coordinates relative to the centre (and their features)."""
+
+    def __init__(self, radius, nsample, use_xyz=True):
+        super().__init__()
+        self.radius, self.nsample, self.use_xyz = radius, nsample, use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        """xyz (B, N, 3), new_xyz (B, npoint, 3), features (B, C, N) or None -> (B, 3 + C, npoint, nsample) (C alone without use_xyz)."""
+        idx = ball_query(self.radius, self.nsample, xyz, new_xyz)
+        grouped_xyz = grouping_operation(xyz.transpose(1, 2).contiguous(), idx) - new_xyz.transpose(1, 2).unsqueeze(-1)
+        if features is None:
+            if not self.use_xyz:
+                raise ValueError("QueryAndGroup without features needs use_xyz")
+            return grouped_xyz
+        grouped = grouping_operation(features, idx)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
+
+
+class GroupAll(nn.Module):
+    """One group holding the whole cloud."""
+
+    def __init__(self, use_xyz=True):
+        super().__init__()
+        self.use_xyz = use_xyz
+
+    def forward(self, xyz, new_xyz, features=None):
+        """xyz (B, N, 3), new_xyz ignored, features (B, C, N) or None -> (B, 3 + C, 1, N) (C alone without use_xyz)."""
+        grouped_xyz = xyz.transpose(1, 2).unsqueeze(2)
+        if features is None:
+            return grouped_xyz
+        grouped = features.unsqueeze(2)
+        return torch.cat([grouped_xyz, grouped], dim=1) if self.use_xyz else grouped
+
+
+def furthest_point_sample_np(points, npoint):
+    """points (N, 3) or (B, N, 3), any real dtype (sampled as float32) -> int32 indices (npoint,) or (B, npoint), on device 0."""
+    pts = np.ascontiguousarray(points, dtype=np.float32)
+    if pts.ndim not in (2, 3) or pts.shape[-1] != 3:
+        raise ValueError(f"points must be (N, 3) or (B, N, 3), not {pts.shape}")
+    npoint = _count(npoint, "npoint")
+    if not torch.cuda.is_available():
+        raise RuntimeError("furthest_point_sample_np needs a GPU: there is no host path")
+    dev = torch.from_numpy(pts.reshape((-1,) + pts.shape[-2:])).to("cuda")
+    idx = furthest_point_sample(dev, npoint).cpu().numpy()
+    return idx[0] if pts.ndim == 2 else idx
