@@ -268,8 +268,13 @@ PCR_API int pcr_voxel_filter_cloud(pcr_ctx* ctx, const pcr_cloud* in, double lea
 
 /* --------------------------------------------------------------------- ISS
  * Keypoint_detection_ISS/ISS.py:35-73.  lambdas_out (n,3) descending eigenvalues
- * of the weighted scatter; counts_out[n] = |N(p_i)| (inclusive radius, self
- * included).  keypoints_out holds up to max_keypoints + 1 indices after NMS
+ * of the weighted scatter; counts_out[n] = |N(p_i)| (self included).  "Within
+ * radius" is scipy's query_ball_point, for the neighbourhoods and for the
+ * suppression alike: (dx*dx + dy*dy) + dz*dz <= radius * radius in binary64
+ * (not pcr_radius's sqrt(d2) <= radius, which takes up to an ulp more of d2).
+ * A cloud whose largest extent exceeds 2^18 radii is refused with
+ * PCR_E_UNSUPPORTED: the grid cannot hold a cell of the radius's size.
+ * keypoints_out holds up to max_keypoints + 1 indices after NMS
  * (ISS.py:72-73 stops once MORE than iss_count were taken).  lambdas_out and
  * counts_out may be NULL (they are 28 bytes per point over PCIe); at least
  * one of lambdas_out / keypoints_out must be asked for.                       */
@@ -285,7 +290,10 @@ PCR_API int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, double 
  * smallest eigenvalue of the covariance of its k nearest neighbours (the point
  * itself included, like search_knn_vector_3d on a cloud point); 2 <= k <= 16.
  * normals_out (n,3) by caller row; eigvals_out (n,3) descending and
- * neighbours_out (n,k) ascending (distance, index) may be NULL.             */
+ * neighbours_out (n,k) ascending (distance, index) may be NULL.  A cloud of
+ * n < k points: every row holds the n points in that order, then -1, and the
+ * covariance is of the n points (divisor n-1).  n = 1: the covariance is taken
+ * as zero -- eigenvalues 0, normal (0,0,1), neighbours 0 then -1.            */
 PCR_API int pcr_pca(pcr_ctx* ctx, const pcr_cloud* cloud, double eigvals_out[3], double eigvecs_out[9], double mean_out[3]);
 PCR_API int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* normals_out, double* eigvals_out,
                         int32_t* neighbours_out);
@@ -403,12 +411,13 @@ PCR_API int pcr_match_pairs_fused(pcr_ctx* ctx, const double* descriptors, const
                                   int32_t* corr_out, int32_t* m_out);
 
 /* ------------------------------------------------------------------ DBSCAN
- * DBSCAN.fit (Cluster_dbscan/dbscan.py:10-36), a consumer of the radius query:
+ * DBSCAN.fit (Cluster_dbscan/dbscan.py:10-36):
  * labels_out[n] = cluster id per row (-1 noise), numbered in the reference's
  * discovery order (seeds taken from the END of the index list; a seed needs
  * >= min_pts neighbours, a reached point expands only with > min_pts; a point
- * first met as a noise seed stays noise).  Neighbourhood = distance <= radius,
- * the point itself included (scipy query_ball_point).                        */
+ * first met as a noise seed stays noise).  Neighbourhood = the point itself and
+ * every point with (dx*dx + dy*dy) + dz*dz <= radius * radius in binary64 (scipy
+ * query_ball_point; not pcr_radius's sqrt(d2) <= radius, see pcr_iss).        */
 PCR_API int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts, int32_t* labels_out, int32_t* n_clusters_out);
 
 /* ------------------------------------------------------ ground segmentation

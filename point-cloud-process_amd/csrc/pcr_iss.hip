@@ -165,6 +165,7 @@ iss_nms_kernel(const pcr_pt* __restrict__ pts, const iss_cand* __restrict__ cand
                int* __restrict__ keypoints_out /* mapped host memory */, int* __restrict__ n_out) {
     __shared__ double kx[ISS_NMS_MAX + 1], ky[ISS_NMS_MAX + 1], kz[ISS_NMS_MAX + 1];
     __shared__ int s_first, s_taken;
+    const double nms_r2 = nms_radius >= 0 ? nms_radius * nms_radius : -1.0;   // (a negative radius suppresses nothing)
     if (threadIdx.x == 0) s_taken = 0;
     __syncthreads();
     for (unsigned int base = 0; base < n_cand; base += 256) {
@@ -182,8 +183,7 @@ iss_nms_kernel(const pcr_pt* __restrict__ pts, const iss_cand* __restrict__ cand
             const int taken = s_taken;
             for (; alive && checked < taken; ++checked) {
                 const double dx = kx[checked] - x, dy = ky[checked] - y, dz = kz[checked] - z;
-                const double d = sqrt((dx * dx + dy * dy) + dz * dz);   // the expression of the radius query (pcr_knn.hip)
-                if (!(d > nms_radius)) alive = false;
+                if ((dx * dx + dy * dy) + dz * dz <= nms_r2) alive = false;   // query_ball_point's rule (ISS.py:66), as in the two passes
             }
             checked = taken;
             __syncthreads();
@@ -226,10 +226,16 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     hipSetDevice(ctx->device);
     const int64_t n = cloud->n;
     pcr_index_guard idx(ctx);   // (every scratch block and the index go back on every return path)
-    int rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius * (1.0 + 1e-9), &idx.h);  // block of 27 cells covers the ball with rounding slack
+    const double cell_req = radius * (1.0 + 1e-9);   // block of 27 cells covers the ball with rounding slack
+    int rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, cell_req, &idx.h);
     if (rc) return rc;
-    // the index may have coarsened the cell (huge extents): the 3x3x3 block then still covers the radius
-    if (idx->cell < radius * (1.0 - 1e-12)) return PCR_E_UNSUPPORTED;
+    // The index keeps 2^18 level-0 cells per axis and coarsens the cell of a cloud whose extent is more than 2^18 radii.  The
+    // 3x3x3 block would still cover the ball, but no longer be of its size: both passes would read every point of 27 cells many
+    // radii wide.  That is refused (it never was: this test asked for a SMALLER cell, which the planner never gives).
+    if (idx->cell > cell_req || idx->cell < radius * (1.0 - 1e-12)) {
+        ctx->last_error = "pcr_iss: the cloud's extent exceeds 2^18 radii; the grid cannot hold a cell of the radius";
+        return PCR_E_UNSUPPORTED;
+    }
     pcr_dev_block b_counts(ctx), b_lam(ctx);
     if ((rc = b_counts.alloc(sizeof(int) * n)) || (rc = b_lam.alloc(sizeof(double) * 3 * n))) return rc;
     int* const d_counts = b_counts.as<int>();
@@ -244,12 +250,10 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
         else if ((rc = b_cand.alloc(sizeof(int) * n))) return rc;
         PCR_HIP(ctx, hipMemsetAsync(d_cand_count, 0, sizeof(unsigned int), ctx->stream));
     }
-    // "within radius" is `not (sqrt(d2) > radius)` (the radius query's expression, pcr_knn.hip).  sqrt is monotone and correctly
-    // rounded, so that is `d2 <= r2_in` with r2_in the LARGEST binary64 whose square root does not exceed the radius: same
-    // decisions bit for bit, no square root per candidate (it was most of the VALU work of both passes).
-    double r2_in = radius * radius;
-    while (sqrt(r2_in) > radius) r2_in = nextafter(r2_in, 0.0);
-    while (sqrt(nextafter(r2_in, INFINITY)) <= radius) r2_in = nextafter(r2_in, INFINITY);
+    // "within radius" is scipy's query_ball_point (ISS.py:43,49,66): (dx*dx + dy*dy) + dz*dz <= radius * radius in binary64.  (Not
+    // the kd-tree API's `not (sqrt(d2) > radius)`: that also takes the d2 just above radius * radius whose square root still
+    // rounds to the radius -- one ulp of them at radius 0.5 and at 0.08.)
+    const double r2_in = radius * radius;
     int* const d_cand = b_cand.as<int>();   // (null unless the host suppression wants the list)
     hipLaunchKernelGGL(iss_count_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, r2_in, d_counts);
     hipLaunchKernelGGL(iss_cov_kernel, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, r2_in, (const int*)d_counts, d_lam, gamma21,
@@ -331,6 +335,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
         pcr_pt *const d_rows = b_rows.as<pcr_pt>(), *const d_batch = b_batch.as<pcr_pt>();
         int* const d_ids = b_ids.as<int>();
         std::vector<pcr_pt> kept;
+        const double nms_r2 = nms_radius >= 0 ? nms_radius * nms_radius : -1.0;   // (a negative radius suppresses nothing)
         int taken = 0;
         size_t heap_n = cand.size();
         while (heap_n > 0) {
@@ -352,8 +357,7 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
                 bool alive = true;
                 for (const pcr_pt& k : kept) {
                     const double dx = k.x - c.x, dy = k.y - c.y, dz = k.z - c.z;
-                    const double d = sqrt((dx * dx + dy * dy) + dz * dz);   // the expression of the radius query (pcr_knn.hip)
-                    if (!(d > nms_radius)) { alive = false; break; }
+                    if ((dx * dx + dy * dy) + dz * dz <= nms_r2) { alive = false; break; }   // query_ball_point's rule (ISS.py:66)
                 }
                 if (!alive) continue;
                 kept.push_back(c);

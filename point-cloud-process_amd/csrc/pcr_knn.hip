@@ -145,9 +145,12 @@ knn_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, i
     }
 }
 
+// Membership is `!(d2 > r2_in)` on the squared distance, with the threshold chosen by the caller: pcr_radius and pcr_radius_small
+// pass radius_r2_of_norm_rule(radius), which decides bit for bit like result_set.py:80 on the distance itself; pcr_dbscan passes
+// radius * radius, scipy's query_ball_point.  (A NaN distance is a member under both, as it was with the test on sqrt(d2).)
 struct radius_scan {
     const pcr_pt* pts;
-    double ax, ay, az, radius;
+    double ax, ay, az, r2_in;
     int lane;
     unsigned int count;        // wave-uniform running count
     int* idx_out;              // null in the count pass
@@ -163,8 +166,9 @@ struct radius_scan {
             long long id = 0;
             if (j < e) {
                 const pcr_pt b = pts[j];
-                d = sqrt(dist2(ax, ay, az, b));
-                hit = !(d > radius);  // RadiusNNResultSet.add_point rejects dist > radius (result_set.py:80)
+                const double d2 = dist2(ax, ay, az, b);
+                d = sqrt(d2);
+                hit = !(d2 > r2_in);
                 id = b.id;
             }
             const unsigned long long m = __ballot(hit);
@@ -181,7 +185,7 @@ struct radius_scan {
 };
 
 __global__ void __launch_bounds__(256)
-radius_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, double radius, long long* __restrict__ counts_out,
+radius_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq, double radius, double r2_in, long long* __restrict__ counts_out,
               const long long* __restrict__ offsets, int* __restrict__ idx_out, double* __restrict__ dist_out) {
     __shared__ cell_entry s_stack[4][KN_STACK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -192,13 +196,13 @@ radius_kernel(pcr_grid_view gv, const double* __restrict__ queries, long long nq
     sc.ax = queries[3 * qi];
     sc.ay = queries[3 * qi + 1];
     sc.az = queries[3 * qi + 2];
-    sc.radius = radius;
+    sc.r2_in = r2_in;
     sc.lane = lane;
     sc.count = 0;
     sc.idx_out = offsets ? idx_out : nullptr;
     sc.dist_out = dist_out;
     sc.base = offsets ? offsets[qi] : 0;
-    double bound2 = radius * radius * (1.0 + 1e-12);  // conservative cell pruning; membership is tested on sqrt(d2)
+    double bound2 = radius * radius * (1.0 + 1e-12);  // conservative cell pruning; membership is tested against r2_in
     kn_descend(gv, sc.ax, sc.ay, sc.az, bound2, s_stack[wave], lane, sc);
     if (lane == 0 && !offsets) counts_out[qi] = sc.count;
 }
@@ -594,7 +598,7 @@ knn_tile_kernel(pcr_grid_view gv, const double* __restrict__ queries, const unsi
 // query's neighbours go, unordered, straight into a pinned, device-mapped block of `cap` entries per query (what lies beyond is
 // only counted); the host orders them.  No count pass, no offsets, no device scratch, no copy.
 __global__ void __launch_bounds__(256)
-radius_small_kernel(pcr_grid_view gv, const double* __restrict__ queries, int nq, double radius, unsigned int cap, unsigned int* __restrict__ counts_out,
+radius_small_kernel(pcr_grid_view gv, const double* __restrict__ queries, int nq, double radius, double r2_in, unsigned int cap, unsigned int* __restrict__ counts_out,
                     int* __restrict__ idx_out, double* __restrict__ dist_out) {
     __shared__ cell_entry s_stack[4][KN_STACK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -605,7 +609,7 @@ radius_small_kernel(pcr_grid_view gv, const double* __restrict__ queries, int nq
     sc.ax = queries[3 * qi];
     sc.ay = queries[3 * qi + 1];
     sc.az = queries[3 * qi + 2];
-    sc.radius = radius;
+    sc.r2_in = r2_in;
     sc.lane = lane;
     sc.count = 0;
     sc.idx_out = idx_out;
@@ -615,6 +619,15 @@ radius_small_kernel(pcr_grid_view gv, const double* __restrict__ queries, int nq
     double bound2 = radius * radius * (1.0 + 1e-12);
     kn_descend(gv, sc.ax, sc.ay, sc.az, bound2, s_stack[wave], lane, sc);
     if (lane == 0) counts_out[qi] = sc.count;
+}
+
+// RadiusNNResultSet.add_point rejects dist > radius on dist = sqrt(d2) (result_set.py:80).  sqrt is monotone and correctly rounded,
+// so that is `!(d2 > t)` with t the LARGEST binary64 whose square root does not exceed the radius: the same decisions bit for bit.
+static double radius_r2_of_norm_rule(double radius) {
+    double t = radius * radius;
+    while (sqrt(t) > radius) t = nextafter(t, 0.0);
+    while (t < INFINITY && sqrt(nextafter(t, INFINITY)) <= radius) t = nextafter(t, INFINITY);
+    return t;
 }
 
 // pinned, device-mapped landing block for the few-query paths (grown on demand, kept with the context)
@@ -704,7 +717,7 @@ int pcr_radius_small(pcr_ctx* ctx, const pcr_index* index, const double* queries
     int rc = small_block(ctx, bytes, &h, &d);
     if (rc) return rc;
     memcpy(h, queries, 24 * (size_t)q);
-    hipLaunchKernelGGL(radius_small_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, index->view, (const double*)d, q, radius, (unsigned int)cap,
+    hipLaunchKernelGGL(radius_small_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, index->view, (const double*)d, q, radius, radius_r2_of_norm_rule(radius), (unsigned int)cap,
                        (unsigned int*)(d + o_cnt), (int*)(d + o_idx), (double*)(d + o_d));
     PCR_HIP(ctx, hipGetLastError());
     if ((rc = pcr_wait_flag(ctx, nullptr))) return rc;
@@ -788,9 +801,10 @@ int pcr_radius(pcr_ctx* ctx, const pcr_index* index, const double* queries, int6
     if ((rc = d_q.alloc(sizeof(double) * 3 * q))) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(d_q.p, queries, sizeof(double) * 3 * q, hipMemcpyHostToDevice, ctx->stream));
     const unsigned grid = (unsigned)((q + 3) / 4);
+    const double r2_in = radius_r2_of_norm_rule(radius);
     if (!offsets) {
         if ((rc = d_counts.alloc(sizeof(long long) * q))) return rc;
-        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q.as<const double>(), (long long)q, radius,
+        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q.as<const double>(), (long long)q, radius, r2_in,
                            d_counts.as<long long>(), (const long long*)nullptr, (int*)nullptr, (double*)nullptr);
         PCR_HIP(ctx, hipGetLastError());
         PCR_HIP(ctx, hipMemcpyAsync(counts_out, d_counts.p, sizeof(long long) * q, hipMemcpyDeviceToHost, ctx->stream));
@@ -807,7 +821,7 @@ int pcr_radius(pcr_ctx* ctx, const pcr_index* index, const double* queries, int6
     if (total > 0xffffffffll) { ctx->last_error = "pcr_radius: more than 2^32 - 1 neighbours in one call; split the queries"; return PCR_E_UNSUPPORTED; }
     if ((rc = d_offs.alloc(sizeof(long long) * (q + 1))) || (rc = d_idx.alloc(sizeof(int) * (total + 1))) || (rc = d_dist.alloc(sizeof(double) * (total + 1)))) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(d_offs.p, offsets, sizeof(long long) * (q + 1), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q.as<const double>(), (long long)q, radius,
+    hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q.as<const double>(), (long long)q, radius, r2_in,
                        (long long*)nullptr, d_offs.as<const long long>(), d_idx.as<int>(), d_dist.as<double>());
     PCR_HIP(ctx, hipGetLastError());
     // Ascending distance (ties by index) inside every query's segment, on the device: two stable segmented radix sorts (by
@@ -836,8 +850,10 @@ int pcr_radius(pcr_ctx* ctx, const pcr_index* index, const double* queries, int6
 }
 
 
-// DBSCAN.fit of Cluster_dbscan/dbscan.py:10-36 -- a consumer of the radius query.  All N radius queries
-// run on the device (count pass + fill pass of radius_kernel); the labelling loop is the reference's own sequential
+// DBSCAN.fit of Cluster_dbscan/dbscan.py:10-36.  All N neighbourhoods are found on the device (count pass +
+// fill pass of radius_kernel) by scipy's query_ball_point rule, (dx*dx + dy*dy) + dz*dz <= radius * radius -- not by the kd-tree
+// API's rule on the distance, which also takes the d2 just above radius * radius whose square root still rounds to the radius
+// (one ulp of them at radius 0.5 and at 0.08).  The labelling loop is the reference's own sequential
 // traversal, run on the host over the neighbour lists, so labels match the reference's including its quirks: seeds are
 // popped from the END of the index list, a seed needs >= min_pts neighbours (self included) but a reached point only
 // expands with > min_pts, and a point first popped as a noise seed is never relabelled.
@@ -852,6 +868,7 @@ int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts,
     std::vector<long long> counts((size_t)n), offs((size_t)n + 1, 0);
     std::vector<int> nbr;
     const unsigned grid = (unsigned)((n + 3) / 4);
+    const double r2_in = radius * radius;   // scipy's rule, not radius_r2_of_norm_rule: see above
     {   // (the index and the scratch blocks live for the device part only)
         pcr_index_guard index(ctx);
         if ((rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, radius > 0 ? radius : 0.0, &index.h))) return rc;
@@ -860,7 +877,7 @@ int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts,
         const double* const d_q = b_q.as<const double>();
         long long *const d_counts = b_counts.as<long long>(), *const d_offs = b_offs.as<long long>();
         hipMemcpyAsync(b_q.p, xyz.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream);
-        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius, d_counts,
+        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius, r2_in, d_counts,
                            (const long long*)nullptr, (int*)nullptr, (double*)nullptr);
         hipMemcpyAsync(counts.data(), d_counts, sizeof(long long) * n, hipMemcpyDeviceToHost, ctx->stream);
         if (pcr_sync(ctx->stream) != hipSuccess) return PCR_E_HIP;
@@ -868,7 +885,7 @@ int pcr_dbscan(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int min_pts,
         const long long total = offs[(size_t)n];
         if ((rc = b_idx.alloc(sizeof(int) * (total + 1))) || (rc = b_dist.alloc(sizeof(double) * (total + 1)))) return rc;
         hipMemcpyAsync(d_offs, offs.data(), sizeof(long long) * (n + 1), hipMemcpyHostToDevice, ctx->stream);
-        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius,
+        hipLaunchKernelGGL(radius_kernel, dim3(grid), dim3(256), 0, ctx->stream, index->view, d_q, (long long)n, radius, r2_in,
                            (long long*)nullptr, (const long long*)d_offs, b_idx.as<int>(), b_dist.as<double>());
         nbr.resize((size_t)total + 1);
         hipMemcpyAsync(nbr.data(), b_idx.p, sizeof(int) * total, hipMemcpyDeviceToHost, ctx->stream);
