@@ -709,6 +709,52 @@ PCR_API int pcr_pn2_gather_points(void* stream, int b, int c, int n, int npoints
 PCR_API int pcr_pn2_group_points(void* stream, int b, int c, int n, int npoints, int nsample, const float* points /* b,c,n */,
                                  const int32_t* idx /* b,npoints,nsample */, float* out /* b,c,npoints,nsample */);
 
+/* ----------------------------------------------------------- object batches
+ * The stage between DBSCAN's labels and the classifier's input: `preprocess` of Final_Project/scripts/detect.py:269-354, whose
+ * resampling step also builds the training set (generating-training-set.py:186-194).  All arithmetic is binary64 on the stored
+ * coordinates, in the order written here, without contraction, so that NumPy / SciPy give the same bits.
+ *
+ * pcr_objects_build groups the rows of a device-resident cloud by labels[row] (n entries BY CALLER ROW, whatever the order of the
+ * records on the device: pcr_cloud_reordered).  A label < 0 is noise and belongs to no object; a label >= n_objects: PCR_E_INVALID
+ * (checked before any launch); an id without rows is an object of count 0.  Within an object the rows stay in ascending caller row
+ * (points[object_ids == o], detect.py:295).  Empty cloud: PCR_E_EMPTY; more than 2^31 - 1 rows: PCR_E_UNSUPPORTED.  The handle keeps
+ * the grouped records and the statistics on the device and does not refer to the cloud afterwards.
+ *   offsets[n_objects + 1]: object o owns [offsets[o], offsets[o+1]) of the grouped order; offsets[n_objects] = m, the labelled rows.
+ *   rows[m]: the caller rows in the grouped order.
+ *   stats, each output optional: count[o] = offsets[o+1] - offsets[o] ((object_ids == o).sum(), detect.py:286);
+ *     mean[3o + a] = (((c_0 + c_1) + c_2) + ...) / (double)count over the object's rows in ascending order (np.mean(axis=0),
+ *     detect.py:290 and :312); bmin / bmax the axis-aligned box (detect.py:244).  An object of count 0: mean NaN (0.0 / 0.0, like
+ *     np.mean of nothing), bmin +inf, bmax -inf.
+ * pcr_objects_select, on the host (no context; counterpart of pcr_ground_select): keep[o] = count[o] > min_count (detect.py:286 with
+ *   min_count = 4: five rows are kept) and sqrt(mx*mx + my*my) <= max_radius (detect.py:291 skips on >, so a centre exactly on the
+ *   radius is kept).  A NaN centre is dropped: the reference's comparison would let it pass and np.random.choice then refuses its
+ *   weights.
+ * pcr_objects_weights: weights[k] for every grouped row k, unnormalised (detect.py:299-301):
+ *     w_i = (((d_i0 + d_i1) + d_i2) + ... + d_i,n-1) / (double)n,  j ascending over ALL n rows of i's object, d_ii = +0.0 included,
+ *     d_ij = sqrt(((dx*dx) + dy*dy) + dz*dz), dx = x_i - x_j, ...                 (pdist 'euclidean', then the column mean)
+ *   keep (n_objects flags, or NULL = every object): rows of an object that is not kept get 0.  The n x n matrix is never stored; a
+ *   wave owns 64 rows i and stages the rows j through on-chip memory PCR_OBJECTS_TILE at a time.  `weights /= weights.sum()`
+ *   (detect.py:302) is NumPy's pairwise sum and stays with the caller.
+ * pcr_objects_pack_f32 fills the classifier's batch (detect.py:311-318, then .float()) at a DEVICE address of the context's device:
+ *   slot s (of b) shows object slot_object[s]; local_idx[s*S + k] is a position within that object in ascending row order, which is
+ *   what np.random.choice(np.arange(N), ...) returns (detect.py:304).  out[s][k] = { (float)(x - mean_x), (float)(y - mean_y),
+ *   (float)(z - mean_z), (float)nx, (float)ny, (float)nz }: the subtraction in binary64 with the mean of pcr_objects_stats, then
+ *   rounded to nearest; normals (n x 3 binary64 on the host, BY CALLER ROW) may be NULL, and the rows are then 3 floats.  C-contiguous
+ *   (b, S, 6) or (b, S, 3).  The call returns after the context's stream has drained: the caller's framework may read the tensor at
+ *   once (it must have finished its own earlier work on that memory).  PCR_E_INVALID, before any launch: an object outside
+ *   [0, n_objects), an index outside [0, count), a NULL array.  b == 0 or S == 0: PCR_OK, nothing is launched.                       */
+#define PCR_OBJECTS_TILE 128
+typedef struct pcr_objects pcr_objects;
+PCR_API int pcr_objects_build(pcr_ctx* ctx, const pcr_cloud* cloud, const int32_t* labels /* n, by caller row */, int32_t n_objects, pcr_objects** out);
+PCR_API int pcr_objects_free(pcr_ctx* ctx, pcr_objects* objs);
+PCR_API int pcr_objects_offsets(const pcr_objects* objs, int64_t* offsets /* n_objects + 1 */);
+PCR_API int pcr_objects_rows(pcr_ctx* ctx, const pcr_objects* objs, int32_t* rows /* m */);
+PCR_API int pcr_objects_stats(pcr_ctx* ctx, const pcr_objects* objs, int64_t* count /* n_objects */, double* mean /* n_objects*3 */, double* bmin, double* bmax);
+PCR_API int pcr_objects_select(const int64_t* count, const double* mean, int32_t n_objects, int64_t min_count, double max_radius, uint8_t* keep /* n_objects */);
+PCR_API int pcr_objects_weights(pcr_ctx* ctx, const pcr_objects* objs, const uint8_t* keep /* n_objects or NULL */, double* weights /* m */);
+PCR_API int pcr_objects_pack_f32(pcr_ctx* ctx, const pcr_objects* objs, const double* normals /* n*3 or NULL */, const int32_t* slot_object /* b */,
+                                 const int64_t* local_idx /* b*S */, int64_t b, int64_t S, void* out_device /* b*S*(6 or 3) floats */);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

@@ -53,6 +53,8 @@ from .global_registration import (  # noqa: F401
 )
 from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
+from . import objects  # noqa: F401
+from .objects import ObjectBatch, object_stats, preprocess, preprocess_device, resample_weights  # noqa: F401
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
 from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401

@@ -37,6 +37,7 @@ PCR_GMM_MAX_K = 32
 PCR_KMEANS_MAX_K = 32
 PCR_SPECTRAL_MAX_K = 8
 PCR_SPECTRAL_MAX_NNK = 15
+PCR_OBJECTS_TILE = 128
 
 
 class IcpParams(C.Structure):
@@ -352,6 +353,15 @@ SIGNATURES = {
     "pcr_pn2_three_interpolate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "pcr_pn2_gather_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "pcr_pn2_group_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    # object batches: (ctx, objects handle, host arrays...); the pack's last argument is the address of the caller's device tensor
+    "pcr_objects_build": (C.c_int, [_vp, _vp, _ip, C.c_int32, C.POINTER(_vp)]),
+    "pcr_objects_free": (C.c_int, [_vp, _vp]),
+    "pcr_objects_offsets": (C.c_int, [_vp, _lp]),
+    "pcr_objects_rows": (C.c_int, [_vp, _vp, _ip]),
+    "pcr_objects_stats": (C.c_int, [_vp, _vp, _lp, _dp, _dp, _dp]),
+    "pcr_objects_select": (C.c_int, [_lp, _dp, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_uint8)]),
+    "pcr_objects_weights": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint8), _dp]),
+    "pcr_objects_pack_f32": (C.c_int, [_vp, _vp, _dp, _ip, _lp, C.c_int64, C.c_int64, _vp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),
