@@ -709,6 +709,43 @@ PCR_API int pcr_pn2_gather_points(void* stream, int b, int c, int n, int npoints
 PCR_API int pcr_pn2_group_points(void* stream, int b, int c, int n, int npoints, int nsample, const float* points /* b,c,n */,
                                  const int32_t* idx /* b,npoints,nsample */, float* out /* b,c,npoints,nsample */);
 
+/* Set abstraction for inference, fused: gather, shared MLP (batch norm folded into the weights by the caller), ReLU and the maximum
+ * over the ball in one kernel; the grouped tensor (b, C, m, nsample) is never stored.  Same calling rules as the ops above.  `widths`,
+ * `weights` and `biases` are HOST arrays of n_layers entries (read during the call); weights[l] and biases[l] are device pointers,
+ * layer l's matrix (widths[l], K_l) row-major with K_l = widths[l-1] (K_0 below) and its bias (widths[l]).  `feats` is POINT-major
+ * (b, n, c_feat), so a row's gather is one contiguous read; NULL iff c_feat == 0.  Element (bi, j, ci) of the result is
+ * out[bi*out_batch_stride + j*m + ci]: with out_batch_stride = (sum of all scales' widths) * m every scale of a multi-scale module
+ * writes straight into its channel range of the concatenated (b, sum C, m) tensor.
+ * Contract.  All arithmetic is binary32, no contraction in the VALU parts.
+ *   - The row for (centre ci, sample s) is built from p = idx[bi, ci, s].  With use_xyz its first three entries are
+ *     xyz[bi, p, :] - new_xyz[bi, ci, :]; then follow feats[bi, p, 0:c_feat].  K_0 = 3*use_xyz + c_feat, which must be at least 1.
+ *   - Layer l computes acc = bias_l[j], then for k = 0 .. K_l-1 in ascending order acc = fmaf(x[k], W_l[j,k], acc), then
+ *     y[j] = acc > 0 ? acc : +0.
+ *   - out[bi, j, ci] = max over s of y_last[j].  Every y is at least +0, so the maximum has no sign or NaN cases on finite input.
+ *     Inputs must be finite and indices in range; neither is validated, as for the other ops.
+ *   - Padding rows never enter the maximum: a tile row that stands for no (ci, s) pair is a copy of a real row of the same unit and
+ *     is masked out of the pooling; it is never a row of zeros, whose relu(bias) could win the maximum.
+ *   - There is no cross-workgroup floating-point accumulation; in this implementation no two workgroups share a centre at all (a
+ *     workgroup owns whole centres), so every (bi, j, ci) is stored once, `out` needs no zeroing and elements outside the addressed
+ *     ones are not touched.  The result is bitwise repeatable.
+ *   - PCR_OK for a normal call; PCR_E_INVALID for a negative size, nsample < 1 or n < 1 with a non-empty output, K_0 < 1,
+ *     n_layers < 1, a width below 1, or a NULL pointer where data is needed; PCR_E_UNSUPPORTED, before any launch, for a shape the
+ *     kernel declines; PCR_E_HIP for a failed launch.  An empty output (b == 0 or m == 0) returns PCR_OK and launches nothing.
+ *   - Supported: 1 to PCR_PN2_SA_MAX_LAYERS layers, every width at most PCR_PN2_SA_MAX_WIDTH, K_0 at most PCR_PN2_SA_MAX_K0, at
+ *     most 2^31 - 1 workgroups.  The width limit is the on-chip budget: a workgroup keeps a 64-row tile of one layer's activations
+ *     in LDS (64 x 257 floats) beside a 32-column stage of the weights (256 x 33) and of the gathered rows (64 x 33), 107 KiB of
+ *     160, and the tile's accumulators in registers (64 per lane at width 256).  K_0 is streamed 32 columns at a time and is not
+ *     bounded by LDS; 1024 is the range that is tested.  This covers every module of the reference's classifiers that has centres
+ *     (K_0 up to 323, widths up to 256).                                                                                          */
+#define PCR_PN2_SA_MAX_LAYERS 3
+#define PCR_PN2_SA_MAX_WIDTH 256
+#define PCR_PN2_SA_MAX_K0 1024
+PCR_API int pcr_pn2_sa_mlp_max(void* stream, int b, int n, int m, int nsample, int c_feat, int use_xyz, const float* xyz /* b,n,3 */,
+                               const float* new_xyz /* b,m,3 */, const float* feats /* b,n,c_feat or NULL */,
+                               const int32_t* idx /* b,m,nsample */, int n_layers, const int* widths /* host, n_layers */,
+                               const float* const* weights /* host, n_layers device pointers */,
+                               const float* const* biases /* host, n_layers device pointers */, float* out, long long out_batch_stride);
+
 /* ----------------------------------------------------------- object batches
  * The stage between DBSCAN's labels and the classifier's input: `preprocess` of Final_Project/scripts/detect.py:269-354, whose
  * resampling step also builds the training set (generating-training-set.py:186-194).  All arithmetic is binary64 on the stored

@@ -54,7 +54,7 @@ from .global_registration import (  # noqa: F401
 from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from . import objects  # noqa: F401
-from .objects import ObjectBatch, object_stats, preprocess, preprocess_device, resample_weights  # noqa: F401
+from .objects import ObjectBatch, object_stats, predict, preprocess, preprocess_device, resample_weights  # noqa: F401
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
 from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401
@@ -67,7 +67,8 @@ __version__ = "0.1.0"
 
 # The PointNet++ ops are torch modules and autograd functions: they come in on first use, so that importing the package does not
 # import torch (see PCR_NO_TORCH_PRELOAD in _lib.py).
-_POINTNET2_EXPORTS = ("pointnet2_ops", "pointnet2_utils", "pointnet2_modules", "furthest_point_sample_np")
+_POINTNET2_EXPORTS = ("pointnet2_ops", "pointnet2_utils", "pointnet2_modules", "furthest_point_sample_np", "pointnet2_models",
+                      "PointNet2ClassificationSSG", "PointNet2ClassificationMSG")
 
 
 def __getattr__(name):

@@ -353,6 +353,9 @@ SIGNATURES = {
     "pcr_pn2_three_interpolate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "pcr_pn2_gather_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "pcr_pn2_group_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    # (stream, b, n, m, nsample, c_feat, use_xyz, xyz, new_xyz, feats, idx, n_layers, host widths, host weight / bias pointer arrays, out, stride)
+    "pcr_pn2_sa_mlp_max": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int),
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, C.c_longlong]),
     # object batches: (ctx, objects handle, host arrays...); the pack's last argument is the address of the caller's device tensor
     "pcr_objects_build": (C.c_int, [_vp, _vp, _ip, C.c_int32, C.POINTER(_vp)]),
     "pcr_objects_free": (C.c_int, [_vp, _vp]),

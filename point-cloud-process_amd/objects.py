@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib as L
 from .device import DeviceCloud, default_context, points_of
 
-__all__ = ["ObjectBatch", "object_stats", "resample_weights", "preprocess", "preprocess_device", "TILE"]
+__all__ = ["ObjectBatch", "object_stats", "resample_weights", "preprocess", "preprocess_device", "predict", "TILE"]
 
 TILE = L.PCR_OBJECTS_TILE   # rows j per stage of the weights kernel (include/pcr.h)
 _u8p = C.POINTER(C.c_uint8)
@@ -290,3 +290,33 @@ def preprocess_device(segmented_objects, object_ids, config, ctx=None, *, normal
         batch.free()
         if owned:
             cloud.free()
+
+
+def predict(X, object_ids, N, model, config):
+    """detect.py:357-412 behind its ``preprocess`` -> ``{class_id: {object_id: confidence}}`` for ``class_id`` in
+    ``range(config['num_classes'])``.  ``X, object_ids, N`` are what ``preprocess_device`` returns: the (B_padded, S, channels) float32
+    batch, the id behind every slot and the unpadded count.  The model (put into eval mode, as the reference does) sees whole batches
+    of ``config['batch_size']`` slots under ``torch.no_grad()`` -- a classifier of ``pointnet2_models`` then runs its fused path --
+    and every slot gets ``argmax`` and ``max`` of the softmax of its logits.  Slots from N on are padding and are skipped; the
+    entries are inserted in slot order, the reference's.  N = 0: every class has an empty dict and the model is not called."""
+    import torch   # lazily: importing the package does not import torch
+    import torch.nn.functional as F
+
+    predictions = {class_id: {} for class_id in range(int(config["num_classes"]))}
+    batch_size = int(config["batch_size"])
+    N = int(N)
+    if N <= 0:
+        return predictions
+    if N > len(X) or len(object_ids) != len(X):
+        raise ValueError(f"X has {len(X)} slots and object_ids {len(object_ids)}, N is {N}")
+    if hasattr(model, "eval"):
+        model.eval()
+    for first in range(0, (len(X) // batch_size) * batch_size, batch_size):
+        if first >= N:
+            break
+        with torch.no_grad():
+            logits = model(X[first:first + batch_size])
+        prob_score = F.softmax(logits, dim=1).cpu().numpy()
+        for slot, class_id, confidence in zip(range(first, min(first + batch_size, N)), np.argmax(prob_score, axis=1), np.max(prob_score, axis=1)):
+            predictions[int(class_id)][object_ids[slot]] = confidence
+    return predictions

@@ -9,6 +9,7 @@ from typing import List, Optional, Tuple
 import torch
 import torch.nn as nn
 
+from .. import _lib
 from . import pointnet2_utils
 
 
@@ -23,12 +24,99 @@ def build_shared_mlp(mlp_spec: List[int], bn: bool = True):
     return nn.Sequential(*layers)
 
 
+def fold_shared_mlp(mlp):
+    """The layers of a ``build_shared_mlp`` sequence in eval mode as ``[(W', b'), ...]``, float32 on the module's device, with each
+    batch norm folded into the convolution in front of it so that a layer is ``relu(W' x + b')``.  Computed in binary64 and rounded
+    once: ``s = gamma / sqrt(running_var + eps)``, ``W' = W * s`` per output row, ``b' = beta - running_mean * s (+ conv_bias * s)``;
+    a convolution without batch norm keeps its own weight and bias.  A module in training mode raises (its batch norm would use
+    the batch's statistics)."""
+    if mlp.training:
+        raise ValueError("fold_shared_mlp needs a module in eval mode: in training mode batch norm uses the batch's statistics")
+    layers = list(mlp)
+    folded = []
+    i = 0
+    with torch.no_grad():
+        while i < len(layers):
+            conv = layers[i]
+            if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (1, 1) or conv.groups != 1:
+                raise ValueError(f"layer {i} of the shared MLP is not a 1x1 convolution: {conv!r}")
+            i += 1
+            W = conv.weight.detach().to(torch.float64).reshape(conv.out_channels, conv.in_channels)
+            bias = conv.bias.detach().to(torch.float64) if conv.bias is not None else torch.zeros(conv.out_channels, dtype=torch.float64, device=W.device)
+            if i < len(layers) and isinstance(layers[i], nn.BatchNorm2d):
+                bn = layers[i]
+                i += 1
+                if bn.running_var is None or bn.running_mean is None:
+                    raise ValueError("a batch norm without running statistics cannot be folded")
+                s = 1.0 / torch.sqrt(bn.running_var.detach().to(torch.float64) + bn.eps)
+                if bn.weight is not None:
+                    s = bn.weight.detach().to(torch.float64) * s
+                beta = bn.bias.detach().to(torch.float64) if bn.bias is not None else torch.zeros_like(s)
+                W = W * s[:, None]
+                bias = beta - bn.running_mean.detach().to(torch.float64) * s + (bias * s if conv.bias is not None else 0.0)
+            if i < len(layers) and isinstance(layers[i], nn.ReLU):
+                i += 1
+            else:
+                raise ValueError("every layer of the shared MLP must end in a ReLU")
+            folded.append((W.to(torch.float32).contiguous(), bias.to(torch.float32).contiguous()))
+    return folded
+
+
 class _PointnetSAModuleBase(nn.Module):
     def __init__(self):
         super().__init__()
         self.npoint = None
         self.groupers = None
         self.mlps = None
+        self._folded = {}
+
+    def _folded_mlp(self, scale):
+        """fold_shared_mlp of one scale, kept until one of its parameters or buffers is written to, replaced or moved."""
+        mlp = self.mlps[scale]
+        try:
+            stamp = tuple((t._version, t.data_ptr()) for t in list(mlp.parameters()) + list(mlp.buffers()))
+        except RuntimeError:     # tensors made in inference mode keep no version: fold every time
+            stamp = None
+        kept = self._folded.get(scale)
+        if kept is None or stamp is None or kept[0] != stamp:
+            kept = (stamp, fold_shared_mlp(mlp))
+            self._folded[scale] = kept
+        return kept[1]
+
+    def fused_forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+        """``forward`` for inference (eval mode, grad disabled; anything else raises): the same sampling and ball query, then per scale
+        ONE kernel (pointnet2_utils.grouped_mlp_max) that gathers, runs the shared MLP with its batch norm folded in and takes the
+        maximum over the ball, writing its channel range of the (B, sum of widths, npoint) result; the grouped tensor is never
+        stored.  A scale that groups everything, or whose shape the kernel declines, goes through ``forward``'s torch path.  Every
+        output is one binary32 fmaf chain per layer (include/pcr.h), so the values differ from ``forward``'s by rounding only."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("fused_forward is for inference: call it on a module in eval() mode under torch.no_grad()")
+        new_xyz = None
+        if self.npoint is not None:
+            picks = pointnet2_utils.furthest_point_sample(xyz, self.npoint)
+            new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), picks).transpose(1, 2).contiguous()
+        widths = [[layer for layer in mlp if isinstance(layer, nn.Conv2d)][-1].out_channels for mlp in self.mlps]
+        B = xyz.shape[0]
+        out = torch.empty((B, sum(widths), self.npoint if self.npoint is not None else 1), dtype=torch.float32, device=xyz.device)
+        features_t = None     # point-major copy, made once and shared by the scales
+        first = 0
+        for scale, (grouper, mlp, width) in enumerate(zip(self.groupers, self.mlps, widths)):
+            dst = out[:, first:first + width]
+            first += width
+            if isinstance(grouper, pointnet2_utils.QueryAndGroup):
+                if features is not None and features_t is None:
+                    features_t = features.transpose(1, 2).contiguous()
+                idx = pointnet2_utils.ball_query(grouper.radius, grouper.nsample, xyz, new_xyz)
+                folded = self._folded_mlp(scale)
+                try:
+                    pointnet2_utils.grouped_mlp_max(xyz, new_xyz, features_t, idx, [w for w, _ in folded], [b for _, b in folded],
+                                                    use_xyz=grouper.use_xyz, out=dst)
+                    continue
+                except _lib.PcrError as err:
+                    if err.status != _lib.PCR_E_UNSUPPORTED:
+                        raise
+            dst.copy_(mlp(grouper(xyz, new_xyz, features)).max(dim=3).values)
+        return new_xyz, out
 
     def forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """xyz (B, N, 3), features (B, C, N) or None -> new_xyz (B, npoint, 3) (None when the module groups everything) and

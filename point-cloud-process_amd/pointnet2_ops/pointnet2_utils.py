@@ -234,6 +234,67 @@ class BallQuery(Function):
 ball_query = BallQuery.apply
 
 
+def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True, out=None):
+    """Set abstraction for inference in one kernel (include/pcr.h, pcr_pn2_sa_mlp_max): per centre the rows of its ball -- relative
+    coordinates (use_xyz), then the point's features -- through the layers ``relu(W x + b)`` and the maximum over the ball; the grouped
+    tensor is never stored.
+
+    xyz (B, N, 3), new_xyz (B, npoint, 3), features_t (B, N, C) POINT-major or None, idx (B, npoint, nsample) int32 (ball_query's),
+    weights[l] (width_l, K_l) and biases[l] (width_l,) float32 with K_0 = 3 * use_xyz + C and K_l = width_(l-1) (fold_shared_mlp of
+    pointnet2_modules gives them) -> (B, width_last, npoint).  `out`: a (B, width_last, npoint) float32 view to write into instead,
+    contiguous in its last two axes (a channel range of a larger (B, C_total, npoint) tensor); it is returned.
+
+    Not differentiable: an input that requires grad while grad is enabled raises ValueError.  A shape the kernel declines raises
+    PcrError with status PCR_E_UNSUPPORTED and has launched nothing."""
+    weights, biases = list(weights), list(biases)
+    if len(weights) != len(biases) or not weights:
+        raise ValueError("weights and biases must be lists of the same length, one entry per layer (at least one)")
+    specs = [(xyz, "xyz", f32, ("B", "N", 3)), (new_xyz, "new_xyz", f32, ("B", "m", 3)), (idx, "idx", i32, ("B", "m", None))]
+    if features_t is not None:
+        specs.append((features_t, "features_t", f32, ("B", "N", None)))
+    for l, (w, bias) in enumerate(zip(weights, biases)):
+        specs += [(w, f"weights[{l}]", f32, (f"w{l}", f"k{l}")), (bias, f"biases[{l}]", f32, (f"w{l}",))]
+    _check(*specs, device=False)
+    c_feat = 0 if features_t is None else features_t.shape[2]
+    k = (3 if use_xyz else 0) + c_feat
+    if k < 1:
+        raise ValueError("grouped_mlp_max without features needs use_xyz")
+    for l, w in enumerate(weights):
+        if w.shape[1] != k:
+            raise ValueError(f"weights[{l}] must have {k} entries along axis 1, not {w.shape[1]}")
+        if w.shape[0] < 1:
+            raise ValueError(f"weights[{l}] must have at least one row")
+        k = w.shape[0]
+    B, N, _ = xyz.shape
+    _, npoint, nsample = idx.shape
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != f32 or tuple(out.shape) != (B, k, npoint):
+            raise ValueError(f"out must be a float32 tensor of shape {(B, k, npoint)}")
+        if B and k and npoint and (out.stride(2) != 1 or out.stride(1) != npoint or (B > 1 and out.stride(0) < k * npoint)):
+            raise ValueError("out must be contiguous in its last two axes, with a batch stride that keeps the batches apart")
+    tensors = [t for t, *_ in specs] + ([out] if out is not None else [])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError("grouped_mlp_max is not differentiable: call it under torch.no_grad() or on tensors that do not require grad")
+    if B and npoint and nsample < 1:
+        raise ValueError("idx has no samples per centre")
+    if B and npoint and N == 0:
+        raise ValueError("xyz has no points to group")
+    _check(*specs)
+    if out is not None and out.device != xyz.device:
+        raise ValueError(f"out is on {out.device}, xyz on {xyz.device}")
+    if out is None:
+        out = torch.empty((B, k, npoint), dtype=f32, device=xyz.device)
+    n_layers = len(weights)
+    C = _lib.C
+    widths = (C.c_int * n_layers)(*[w.shape[0] for w in weights])
+    wptr = (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights])
+    bptr = (C.c_void_p * n_layers)(*[t.data_ptr() for t in biases])
+    _launch(xyz, "pcr_pn2_sa_mlp_max", B, N, npoint, nsample, c_feat, 1 if use_xyz else 0, xyz.data_ptr(), new_xyz.data_ptr(),
+            features_t.data_ptr() if features_t is not None else None, idx.data_ptr(), n_layers, widths, wptr, bptr, out.data_ptr(),
+            out.stride(0) if B > 1 else k * npoint)
+    return out
+
+
 class QueryAndGroup(nn.Module):
     """Ball query around every centre, then the neighbours' coordinates relative to the centre (and their features)."""
 
