@@ -792,6 +792,47 @@ PCR_API int pcr_objects_weights(pcr_ctx* ctx, const pcr_objects* objs, const uin
 PCR_API int pcr_objects_pack_f32(pcr_ctx* ctx, const pcr_objects* objs, const double* normals /* n*3 or NULL */, const int32_t* slot_object /* b */,
                                  const int64_t* local_idx /* b*S */, int64_t b, int64_t S, void* out_device /* b*S*(6 or 3) floats */);
 
+/* -------------------------------------------------------------- KITTI boxes
+ * The per-object part of `to_kitti_eval_format` (Final_Project/scripts/detect.py:106-163 with get_orientation_in_camera_frame,
+ * detect.py:37-54, and transform_coords_utils.py): the 2-D pixel box, the camera-frame centre, the PCA heading on the x-z plane and
+ * the extents in the heading-aligned object frame, for every object of a pcr_objects handle in ONE launch (one wave per object).
+ * The calibration matrices are row-major with read_calib's shapes (extract.py:49-84): R0_rect 3x3, Tr_velo_to_cam = T 3x4, P2 = P 3x4.
+ *
+ * Everything is binary64 in exactly this order, without contraction or atomics; nothing depends on arrival order.  Per row (x, y, z):
+ *   u_i = ((T[i][0]*x + T[i][1]*y) + T[i][2]*z) + T[i][3]                   unrectified camera frame
+ *   X_i = (R0[i][0]*u_0 + R0[i][1]*u_1) + R0[i][2]*u_2                      rectified camera frame
+ *   q_i = ((P[i][0]*X_0 + P[i][1]*X_1) + P[i][2]*X_2) + P[i][3],  px = q_0/q_2, py = q_1/q_2   (no special case for q_2 <= 0: the
+ *     reference has none; a NaN pixel coordinate takes no part in the pixel box)
+ * The object sum S over the n rows of an object in grouped order (ascending caller row): p_l, l = 0 .. 63, starts from +0.0 and
+ *   adds rows l, l + 64, ... ascending; then p_l += p_{l+s} for every l < s, for s = 32, 16, 8, 4, 2, 1; the sum is p_0.  This order
+ *   belongs to the ABI, not to the launch shape.
+ *   ctr_i = S(X_i) / (double)n;  d_i = X_i - ctr_i;
+ *   a = S(d_0*d_0) / n, b = S(d_0*d_2) / n, c = S(d_2*d_2) / n       (np.cov(bias=True) of the centred rows without its second
+ *     centring, whose effect is of the order of one rounding of the centre)
+ *   (cs, sn) = pcr_kitti_direction(a, b, c), below;  ry = atan2(sn, cs) is the CALLER's: no transcendental runs on the device.
+ *   object frame (detect.py:135-148 with cos(-ry) = cs, sin(-ry) = -sn):  xo = cs*d_0 - (-sn)*d_2, yo = d_1, zo = (-sn)*d_0 + cs*d_2
+ *   extent per axis = max - min, the max taken as -(min of the negated values).
+ * pcr_kitti_direction (host, no context; the kernel compiles the same source): with h = (a - c)*0.5,
+ *   b == 0:            (1, -0.0) if h > 0, else (0, -1)
+ *   b != 0, h >= 0:    e = (h + r, b)       with r = sqrt(h*h + b*b)
+ *   b != 0, h <  0:    e = (-b, r - h)
+ *   and (cs, sn) = e / sqrt(e0*e0 + e1*e1) in the last two cases.  This is what detect.py:47-54 returns with NumPy 2.2 / OpenBLAS
+ *   0.3.29 (LAPACK dgeev on a symmetric 2x2): the reference reads ROW 0 of the matrix of eigenvectors, sorted by descending
+ *   eigenvalue, so for h < 0 its angle is not the principal axis.  PCR_E_INVALID: cs or sn NULL.
+ * boxes[16*o + ...]: 0..3 left, top, right, bottom (min / max of px, py); 4..6 height = extent of yo, width = extent of xo, length =
+ *   extent of zo; 7..9 ctr; 10..11 cs, sn; 12..14 a, b, c; 15 (double)count.  An object of count 0 or with keep[o] == 0: entries
+ *   0..14 are NaN, entry 15 is the count, and no pass runs for it.  Count 1: extents +0.0, direction (0, -1).
+ * An object of at most PCR_KITTI_LDS_ROWS rows keeps its camera-frame rows on chip between the three passes; a larger one computes
+ *   them again from the grouped records -- the same operations, the same bits.
+ * PCR_E_INVALID, before any launch: objs, calib or boxes NULL, a calibration entry (R0_rect, Tr_velo_to_cam, P2) that is not finite.
+ * No objects: PCR_OK, nothing is launched.  The call returns after the context's stream has drained.                              */
+typedef struct pcr_kitti_calib { double R0_rect[9]; double Tr_velo_to_cam[12]; double P2[12]; double reserved[4]; } pcr_kitti_calib;
+#define PCR_KITTI_BOX_DOUBLES 16
+#define PCR_KITTI_LDS_ROWS 512
+PCR_API int pcr_kitti_direction(double a, double b, double c, double* cs, double* sn);
+PCR_API int pcr_objects_kitti_boxes(pcr_ctx* ctx, const pcr_objects* objs, const pcr_kitti_calib* calib, const uint8_t* keep /* n_objects or NULL */,
+                                    double* boxes /* n_objects*16 */);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

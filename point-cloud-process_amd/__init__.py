@@ -55,6 +55,18 @@ from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from . import objects  # noqa: F401
 from .objects import ObjectBatch, object_stats, predict, preprocess, preprocess_device, resample_weights  # noqa: F401
+from . import detection  # noqa: F401
+from .detection import (  # noqa: F401
+    detect,
+    get_bounding_boxes,
+    get_orientation_in_camera_frame,
+    object_boxes,
+    read_calib,
+    segment_ground_and_objects,
+    to_kitti_eval_format,
+    transform_to_cam,
+    transform_to_pixel,
+)
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
 from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401

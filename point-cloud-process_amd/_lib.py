@@ -38,6 +38,8 @@ PCR_KMEANS_MAX_K = 32
 PCR_SPECTRAL_MAX_K = 8
 PCR_SPECTRAL_MAX_NNK = 15
 PCR_OBJECTS_TILE = 128
+PCR_KITTI_BOX_DOUBLES = 16
+PCR_KITTI_LDS_ROWS = 512
 
 
 class IcpParams(C.Structure):
@@ -173,6 +175,15 @@ class GroundResult(C.Structure):
         ("n_outliers", C.c_int64),
         ("point", C.c_double * 3),
         ("normal", C.c_double * 3),
+        ("reserved", C.c_double * 4),
+    ]
+
+
+class KittiCalib(C.Structure):
+    _fields_ = [
+        ("R0_rect", C.c_double * 9),
+        ("Tr_velo_to_cam", C.c_double * 12),
+        ("P2", C.c_double * 12),
         ("reserved", C.c_double * 4),
     ]
 
@@ -365,6 +376,9 @@ SIGNATURES = {
     "pcr_objects_select": (C.c_int, [_lp, _dp, C.c_int32, C.c_int64, C.c_double, C.POINTER(C.c_uint8)]),
     "pcr_objects_weights": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint8), _dp]),
     "pcr_objects_pack_f32": (C.c_int, [_vp, _vp, _dp, _ip, _lp, C.c_int64, C.c_int64, _vp]),
+    # KITTI boxes: the direction rule on the host, and (ctx, objects handle, calibration, keep flags, n_objects x 16 doubles)
+    "pcr_kitti_direction": (C.c_int, [C.c_double, C.c_double, C.c_double, _dp, _dp]),
+    "pcr_objects_kitti_boxes": (C.c_int, [_vp, _vp, C.POINTER(KittiCalib), C.POINTER(C.c_uint8), _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),

@@ -15,6 +15,11 @@
 //   objects_weights_kernel   one wave per tile, lane i owns row i's running sum; the object's rows go by in ascending order, staged
 //                            through LDS PCR_OBJECTS_TILE at a time and read back as broadcasts.
 // pcr_objects_pack_f32 writes the classifier's float32 batch (detect.py:311-318) into the caller's device tensor.
+// pcr_objects_kitti_boxes is the detector's back end, the per-object part of to_kitti_eval_format (detect.py:106-163):
+//   kitti_boxes_kernel       one wave per object, three passes over its rows: camera frame + pixel box + coordinate sums, the centred
+//                            x-z moments and the heading direction (kitti_direction_rule, shared with the host's
+//                            pcr_kitti_direction), the extents in the heading-aligned frame.  An object of at most PCR_KITTI_LDS_ROWS
+//                            rows keeps its camera-frame rows in LDS between the passes; a larger one computes them again.
 // Every floating-point result is a fixed sequence of binary64 operations without contraction: nothing depends on arrival order.
 #include <cmath>
 #include <cstring>
@@ -190,6 +195,125 @@ objects_pack_kernel(const pcr_pt* __restrict__ recs, const long long* __restrict
     if (normals) {
         const double* const nr = normals + 3 * r.id;
         dst[3] = (float)nr[0]; dst[4] = (float)nr[1]; dst[5] = (float)nr[2];
+    }
+}
+
+// ---------------------------------------------------------------- KITTI boxes (detect.py:37-54 and :106-163)
+constexpr int KB_ROWS = PCR_KITTI_LDS_ROWS;
+static_assert(KB_ROWS % OB_WAVE == 0 && 3 * KB_ROWS * sizeof(double) <= 64 * 1024, "the camera-frame rows of one object, a whole number of wave loads");
+
+struct kb_calib { double T[12], R0[9], P[12]; };   // row-major: Tr_velo_to_cam, R0_rect, P2
+
+// The heading direction of the x-z covariance [[a, b], [b, c]] as detect.py:47-54 reads it off np.linalg.eig (include/pcr.h has the
+// derivation).  One source for pcr_kitti_direction and for the kernel.
+__host__ __device__ inline void kitti_direction_rule(double a, double b, double c, double* cs, double* sn) {
+    const double h = (a - c) * 0.5;
+    if (b == 0.0) {
+        if (h > 0.0) { *cs = 1.0; *sn = -0.0; }
+        else { *cs = 0.0; *sn = -1.0; }
+        return;
+    }
+    const double r = sqrt(h * h + b * b);
+    double e0, e1;
+    if (h >= 0.0) { e0 = h + r; e1 = b; }
+    else { e0 = -b; e1 = r - h; }
+    const double len = sqrt(e0 * e0 + e1 * e1);
+    *cs = e0 / len;
+    *sn = e1 / len;
+}
+
+// transform_to_cam (transform_coords_utils.py:4-32) of one row
+__device__ static inline void kb_cam(const kb_calib& k, const pcr_pt& r, double (&X)[3]) {
+    double u[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) u[i] = ((k.T[4 * i] * r.x + k.T[4 * i + 1] * r.y) + k.T[4 * i + 2] * r.z) + k.T[4 * i + 3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) X[i] = (k.R0[3 * i] * u[0] + k.R0[3 * i + 1] * u[1]) + k.R0[3 * i + 2] * u[2];
+}
+
+// The object sum of include/pcr.h: lane l holds the sum of rows l, l + 64, ...; p_l += p_{l+s} for l < s, s = 32 .. 1; p_0 to every lane.
+// (A lane >= s adds something it never hands on: at step s only lanes below 2s are read.)
+__device__ static inline double kb_total(double p) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) p += __shfl_down(p, s, OB_WAVE);
+    return readlane_f64(p, 0);
+}
+
+// One wave per object.  Rows go to lanes round robin (row j to lane j % 64), so every sum has the order of include/pcr.h whatever
+// the launch looks like.  on_chip: pass 1 leaves the camera-frame rows in LDS and passes 2 and 3 read them back (each lane its own
+// rows: no hand-off between lanes); otherwise the two passes load the records again and repeat kb_cam -- the same operations, the
+// same bits.
+__global__ void __launch_bounds__(OB_WAVE)
+kitti_boxes_kernel(const pcr_pt* __restrict__ recs, const long long* __restrict__ off, const unsigned char* __restrict__ keep, kb_calib k,
+                   double* __restrict__ boxes) {
+    __shared__ double s_X[3][KB_ROWS];
+    const int lane = threadIdx.x;
+    const long long o = blockIdx.x;
+    const long long base = off[o];
+    const int cnt = (int)(off[o + 1] - base);
+    double* const out = boxes + PCR_KITTI_BOX_DOUBLES * o;
+    if (cnt <= 0 || (keep && !keep[o])) {
+        if (lane < PCR_KITTI_BOX_DOUBLES) out[lane] = lane == 15 ? (double)cnt : __longlong_as_double(0x7ff8000000000000ll);
+        return;
+    }
+    const bool on_chip = cnt <= KB_ROWS;
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    const double n = (double)cnt;
+
+    // pass 1: camera frame, pixel box, coordinate sums
+    double sum[3] = {0.0, 0.0, 0.0};
+    double mn[2] = {inf, inf}, ng[2] = {inf, inf};
+    for (int j = lane; j < cnt; j += OB_WAVE) {
+        double X[3], q[3];
+        kb_cam(k, recs[base + j], X);
+        if (on_chip) { s_X[0][j] = X[0]; s_X[1][j] = X[1]; s_X[2][j] = X[2]; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) q[i] = ((k.P[4 * i] * X[0] + k.P[4 * i + 1] * X[1]) + k.P[4 * i + 2] * X[2]) + k.P[4 * i + 3];
+        const double px = q[0] / q[2], py = q[1] / q[2];
+        mn[0] = px < mn[0] ? px : mn[0]; mn[1] = py < mn[1] ? py : mn[1];
+        ng[0] = -px < ng[0] ? -px : ng[0]; ng[1] = -py < ng[1] ? -py : ng[1];
+        sum[0] += X[0]; sum[1] += X[1]; sum[2] += X[2];
+    }
+    double ctr[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ctr[i] = kb_total(sum[i]) / n;
+    const double left = wave_min_f64(mn[0]), top = wave_min_f64(mn[1]), right = -wave_min_f64(ng[0]), bottom = -wave_min_f64(ng[1]);
+
+    // pass 2: centred x-z moments, then the direction in every lane
+    double m[3] = {0.0, 0.0, 0.0};
+    for (int j = lane; j < cnt; j += OB_WAVE) {
+        double X[3];
+        if (on_chip) { X[0] = s_X[0][j]; X[2] = s_X[2][j]; }
+        else kb_cam(k, recs[base + j], X);
+        const double d0 = X[0] - ctr[0], d2 = X[2] - ctr[2];
+        m[0] += d0 * d0; m[1] += d0 * d2; m[2] += d2 * d2;
+    }
+    const double a = kb_total(m[0]) / n, b = kb_total(m[1]) / n, c = kb_total(m[2]) / n;
+    double cs, sn;
+    kitti_direction_rule(a, b, c, &cs, &sn);
+    const double ms = -sn;   // sin(-ry)
+
+    // pass 3: extents in the object frame (detect.py:135-163)
+    double lo[3] = {inf, inf, inf}, hi[3] = {inf, inf, inf};   // hi: minimum of the negated coordinate
+    for (int j = lane; j < cnt; j += OB_WAVE) {
+        double X[3];
+        if (on_chip) { X[0] = s_X[0][j]; X[1] = s_X[1][j]; X[2] = s_X[2][j]; }
+        else kb_cam(k, recs[base + j], X);
+        const double d0 = X[0] - ctr[0], d1 = X[1] - ctr[1], d2 = X[2] - ctr[2];
+        const double v[3] = {cs * d0 - ms * d2, d1, ms * d0 + cs * d2};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { lo[i] = v[i] < lo[i] ? v[i] : lo[i]; hi[i] = -v[i] < hi[i] ? -v[i] : hi[i]; }
+    }
+    double ext[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ext[i] = -wave_min_f64(hi[i]) - wave_min_f64(lo[i]);
+    if (lane == 0) {
+        out[0] = left; out[1] = top; out[2] = right; out[3] = bottom;
+        out[4] = ext[1]; out[5] = ext[0]; out[6] = ext[2];
+        out[7] = ctr[0]; out[8] = ctr[1]; out[9] = ctr[2];
+        out[10] = cs; out[11] = sn;
+        out[12] = a; out[13] = b; out[14] = c;
+        out[15] = n;
     }
 }
 
@@ -374,6 +498,37 @@ int pcr_objects_pack_f32(pcr_ctx* ctx, const pcr_objects* objs, const double* no
     PCR_HIP(ctx, hipGetLastError());
     PCR_HIP(ctx, pcr_sync(ctx->stream));   // the tensor is the caller's framework's from here on
     return PCR_OK;
+}
+
+int pcr_kitti_direction(double a, double b, double c, double* cs, double* sn) {
+    if (!cs || !sn) return PCR_E_INVALID;
+    kitti_direction_rule(a, b, c, cs, sn);
+    return PCR_OK;
+}
+
+int pcr_objects_kitti_boxes(pcr_ctx* ctx, const pcr_objects* objs, const pcr_kitti_calib* calib, const uint8_t* keep, double* boxes) {
+    if (!ctx || !objs || !calib || !boxes) return PCR_E_INVALID;
+    kb_calib k;
+    memcpy(k.T, calib->Tr_velo_to_cam, sizeof(k.T));
+    memcpy(k.R0, calib->R0_rect, sizeof(k.R0));
+    memcpy(k.P, calib->P2, sizeof(k.P));
+    for (double v : k.T) if (!std::isfinite(v)) return PCR_E_INVALID;
+    for (double v : k.R0) if (!std::isfinite(v)) return PCR_E_INVALID;
+    for (double v : k.P) if (!std::isfinite(v)) return PCR_E_INVALID;
+    const size_t n_objects = (size_t)objs->n_objects;
+    if (n_objects == 0) return PCR_OK;
+    hipSetDevice(ctx->device);
+    pcr_dev_block b_boxes(ctx), b_keep(ctx);
+    int rc;
+    if ((rc = b_boxes.alloc(sizeof(double) * PCR_KITTI_BOX_DOUBLES * n_objects))) return rc;
+    if (keep) {
+        if ((rc = b_keep.alloc(n_objects))) return rc;
+        PCR_HIP(ctx, hipMemcpyAsync(b_keep.p, keep, n_objects, hipMemcpyHostToDevice, ctx->stream));
+    }
+    hipLaunchKernelGGL(kitti_boxes_kernel, dim3((unsigned int)n_objects), dim3(OB_WAVE), 0, ctx->stream, (const pcr_pt*)objs->recs, (const long long*)objs->d_off,
+                       b_keep.as<const unsigned char>(), k, b_boxes.as<double>());
+    PCR_HIP(ctx, hipGetLastError());
+    return pcr_d2h_staged(ctx, boxes, b_boxes.p, sizeof(double) * PCR_KITTI_BOX_DOUBLES * n_objects);   // (waits for the stream: `keep` is the caller's again)
 }
 
 }  // extern "C"

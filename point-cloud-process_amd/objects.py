@@ -23,6 +23,17 @@ TILE = L.PCR_OBJECTS_TILE   # rows j per stage of the weights kernel (include/pc
 _u8p = C.POINTER(C.c_uint8)
 
 
+def calib_struct(calib):
+    """read_calib's dict (extract.py:49-84) -> pcr_kitti_calib; the shapes are checked here, finiteness by the library."""
+    cal = L.KittiCalib()
+    for key, shape in (("R0_rect", (3, 3)), ("Tr_velo_to_cam", (3, 4)), ("P2", (3, 4))):
+        m = np.asarray(calib[key], dtype=np.float64)
+        if m.shape != shape:
+            raise ValueError(f"calibration entry {key}: expected shape {shape}, got {m.shape}")
+        getattr(cal, key)[:] = m.reshape(-1).tolist()
+    return cal
+
+
 class ObjectBatch:
     """The labelled rows of a device cloud grouped by object (pcr_objects): ``offsets`` (n_objects + 1,), ``m`` labelled rows."""
 
@@ -92,6 +103,21 @@ class ObjectBatch:
                 raise ValueError(f"expected ({self.n}, 3) normals, got shape {nrm.shape}")
         L.check(L.lib().pcr_objects_pack_f32(self.ctx.handle, self.handle, L.dptr(nrm) if nrm is not None else None, L.iptr(slot), L.lptr(idx),
                                              idx.shape[0], idx.shape[1], C.c_void_p(out_ptr)), self.ctx.handle)
+
+    def kitti_boxes(self, calib, keep=None):
+        """(n_objects, 16) float64, the rows of pcr_objects_kitti_boxes (include/pcr.h, "KITTI boxes"): left, top, right, bottom,
+        height, width, length, centre (3), cs, sn, a, b, c, count.  `calib`: read_calib's dict (``R0_rect``, ``Tr_velo_to_cam``,
+        ``P2``).  Objects without rows or with a `keep` flag of 0 are NaN up to the count."""
+        cal = calib_struct(calib)
+        boxes = np.zeros((self.n_objects, L.PCR_KITTI_BOX_DOUBLES), dtype=np.float64)
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8)
+            if keep.shape != (self.n_objects,):
+                raise ValueError(f"expected {self.n_objects} keep flags, got shape {keep.shape}")
+            kp = keep.ctypes.data_as(_u8p)
+        L.check(L.lib().pcr_objects_kitti_boxes(self.ctx.handle, self.handle, C.byref(cal), kp, L.dptr(boxes)), self.ctx.handle)
+        return boxes
 
     def free(self):
         if self._h:
