@@ -70,9 +70,13 @@ PCR_API int64_t pcr_cloud_size(const pcr_cloud* cloud);
 /* diagnostic: 1 when the cloud's records have been laid out along an index's curve (it was the query cloud of a grid search),
  * 0 when they are still in the caller's row order.  Results never depend on it; searches choose their path by it. */
 PCR_API int pcr_cloud_reordered(const pcr_cloud* cloud);
+/* diagnostic: the caller row of every record in device order (rows_out[position] = row; a permutation of [0, n), the identity
+ * while pcr_cloud_reordered is 0).  A NULL pointer: PCR_E_INVALID. */
+PCR_API int pcr_cloud_order(pcr_ctx* ctx, const pcr_cloud* cloud, int64_t* rows_out /* n */);
 PCR_API int pcr_cloud_free(pcr_ctx* ctx, pcr_cloud* cloud);
-/* Optional: lay the cloud out for queries against `index` now (Morton order of its records; row
- * ids are kept, downloads are unaffected).  pcr_nn1 / pcr_icp do this themselves on first use. */
+/* Optional: lay the cloud out for queries against `index` now (its records along a Hilbert curve over the cloud's own box at the
+ * index's cell, or the Morton curve with PCR_QUERY_CURVE=morton in the environment; row ids are kept, downloads are unaffected).
+ * pcr_nn1 / pcr_icp do this themselves on first use. */
 PCR_API int pcr_cloud_prepare(pcr_ctx* ctx, pcr_cloud* cloud, const pcr_index* index);
 /* PointCloud.transform(T) in place (Registration/main.py:110), T row-major 4x4 */
 PCR_API int pcr_cloud_transform(pcr_ctx* ctx, pcr_cloud* cloud, const double T[16]);

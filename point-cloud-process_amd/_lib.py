@@ -293,6 +293,7 @@ SIGNATURES = {
     "pcr_cloud_download_f64": (C.c_int, [_vp, _vp, _dp]),
     "pcr_cloud_size": (C.c_int64, [_vp]),
     "pcr_cloud_reordered": (C.c_int, [_vp]),
+    "pcr_cloud_order": (C.c_int, [_vp, _vp, _lp]),
     "pcr_cloud_free": (C.c_int, [_vp, _vp]),
     "pcr_cloud_transform": (C.c_int, [_vp, _vp, _dp]),
     "pcr_cloud_prepare": (C.c_int, [_vp, _vp, _vp]),

@@ -655,6 +655,11 @@ __global__ void cloud_rows_kernel(const pcr_pt* __restrict__ in, long long n, pc
     out[p.id] = p;
 }
 
+__global__ void cloud_ids_kernel(const pcr_pt* __restrict__ in, long long n, long long* __restrict__ out) {
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = in[i].id;
+}
+
 int pcr_cloud_rows(pcr_ctx* ctx, const pcr_cloud* c, pcr_pt* d_out) {
     hipLaunchKernelGGL(cloud_rows_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (long long)c->n, d_out);
     PCR_HIP(ctx, hipGetLastError());
@@ -740,6 +745,20 @@ int pcr_cloud_download_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const int64_t*
 
 int64_t pcr_cloud_size(const pcr_cloud* c) { return c ? c->n : 0; }
 int pcr_cloud_reordered(const pcr_cloud* c) { return c && c->morton_sorted ? 1 : 0; }
+
+int pcr_cloud_order(pcr_ctx* ctx, const pcr_cloud* c, int64_t* rows_out) try {
+    if (!ctx || !c || !rows_out) return PCR_E_INVALID;
+    if (c->n <= 0) return PCR_E_EMPTY;
+    hipSetDevice(ctx->device);
+    pcr_dev_block b_ids(ctx);
+    int rc = b_ids.alloc(sizeof(long long) * c->n);
+    if (rc != PCR_OK) return rc;
+    hipLaunchKernelGGL(cloud_ids_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, ctx->stream, (const pcr_pt*)c->d, (long long)c->n, b_ids.as<long long>());
+    PCR_HIP(ctx, hipGetLastError());
+    PCR_HIP(ctx, hipMemcpyAsync(rows_out, b_ids.p, sizeof(long long) * c->n, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, pcr_sync(ctx->stream));
+    return PCR_OK;
+} PCR_CATCH(ctx)
 
 int pcr_cloud_free(pcr_ctx* ctx, pcr_cloud* c) {
     if (!c) return PCR_OK;

@@ -16,10 +16,12 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 #include "pcr_internal.h"
 #include "pcr_grid_build_dev.h"
+#include "pcr_curve.h"
 #include "pcr_sort.h"
 
 // ------------------------------------------------------------ build kernels
@@ -55,11 +57,14 @@ __device__ static inline unsigned long long full_key(K k) { return (unsigned lon
 template <typename K>
 __global__ void __launch_bounds__(256)
 morton_keys_var_kernel(const pcr_pt* __restrict__ pts, long long n, double lox, double loy, double loz, double inv, unsigned long long mask,
-                       K* __restrict__ keys, unsigned int* __restrict__ vals) {
+                       pcr_curve cv, K* __restrict__ keys, unsigned int* __restrict__ vals) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const pcr_pt p = pts[i];
-    keys[i] = (K)(morton_key(p.x, p.y, p.z, lox, loy, loz, inv) & mask);
+    // (a target is always laid out along the Morton curve; a query cloud along the curve its lay-out call picked: pcr_curve.h)
+    keys[i] = cv.mode == PCR_CURVE_HILBERT3         ? (K)hilbert3_key(p.x, p.y, p.z, lox, loy, loz, inv, cv.nb)
+              : cv.mode == PCR_CURVE_HILBERT2_MINOR ? (K)hilbert2_minor_key(p.x, p.y, p.z, lox, loy, loz, inv, cv)
+                                                    : (K)(morton_key(p.x, p.y, p.z, lox, loy, loz, inv) & mask);
     vals[i] = (unsigned int)i;
 }
 
@@ -196,15 +201,15 @@ void pcr_grid_plan(const double lo[3], const double hi[3], long long n, double c
     *levels_out = levels;
 }
 
-// Keys of the varying Morton bits -> stable sort of (key, position) -> records in sorted order (+ cell counts of `levels` levels
+// Keys of the varying bits (`cv`: the Morton key, or a query cloud's curve) -> stable sort of (key, position) -> records in sorted order (+ cell counts of `levels` levels
 // in ctx->h_pinned[0..levels), valid after the next stream synchronisation).  The sorted keys stay in sc->keys2 while sc lives.
 struct sort_scratch {
     pcr_dev_block keys, keys2, vals, vals2, temp;
     explicit sort_scratch(pcr_ctx* ctx) : keys(ctx), keys2(ctx), vals(ctx), vals2(ctx), temp(ctx) {}
 };
 template <typename K>
-static int morton_sort_records(pcr_ctx* ctx, const pcr_pt* in, long long n, const double lo[3], double inv, int end_bit, int levels, pcr_pt* out,
-                               sort_scratch* sc) {
+static int morton_sort_records(pcr_ctx* ctx, const pcr_pt* in, long long n, const double lo[3], double inv, int end_bit, const pcr_curve& cv, int levels,
+                               pcr_pt* out, sort_scratch* sc) {
     int rc;
     if ((rc = sc->keys.alloc(sizeof(K) * (size_t)n)) || (rc = sc->keys2.alloc(sizeof(K) * (size_t)n)) || (rc = sc->vals.alloc(sizeof(unsigned int) * n)) ||
         (rc = sc->vals2.alloc(sizeof(unsigned int) * n)))
@@ -213,8 +218,8 @@ static int morton_sort_records(pcr_ctx* ctx, const pcr_pt* in, long long n, cons
     unsigned int *vals = sc->vals.as<unsigned int>(), *vals2 = sc->vals2.as<unsigned int>();
     const int grid_n = (int)((n + 255) / 256);
     const unsigned long long mask = end_bit >= 64 ? ~0ull : (1ull << end_bit) - 1ull;
-    hipLaunchKernelGGL(morton_keys_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, n, lo[0], lo[1], lo[2], inv, mask, keys, vals);
-    if ((rc = pcr_sort_pairs_arena(ctx, keys, keys2, vals, vals2, (size_t)n, (unsigned int)end_bit, sc->temp))) return rc;
+    hipLaunchKernelGGL(morton_keys_var_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, n, lo[0], lo[1], lo[2], inv, mask, cv, keys, vals);
+    if ((rc = pcr_sort_pairs_arena(ctx, keys, keys2, vals, vals2, (size_t)n, (unsigned int)cv.bits, sc->temp))) return rc;
     unsigned int* h_counts_dev = nullptr;
     if (levels > 0) PCR_HIP(ctx, hipHostGetDevicePointer((void**)&h_counts_dev, ctx->h_pinned, 0));
     hipLaunchKernelGGL(gather_count_kernel<K>, dim3(grid_n), dim3(256), 0, ctx->stream, in, (const unsigned int*)vals2, (const K*)keys2, n, levels, out,
@@ -287,8 +292,9 @@ int pcr_grid_build(pcr_ctx* ctx, const pcr_cloud* tgt, double cell, pcr_index* i
     if ((rc = pcr_dev_alloc(ctx, sizeof(pcr_pt) * n, (void**)&idx->sorted))) return rc;
     sort_scratch sc(ctx);   // (given back stream-ordered behind the launches below)
     const bool k32 = end_bit <= 32;
-    rc = k32 ? morton_sort_records<unsigned int>(ctx, tgt->d, n, lo, inv, end_bit, levels, idx->sorted, &sc)
-             : morton_sort_records<unsigned long long>(ctx, tgt->d, n, lo, inv, end_bit, levels, idx->sorted, &sc);
+    const pcr_curve cv = pcr_curve_pick(lo, hi, inv, end_bit, true);   // the tables need the Morton order
+    rc = k32 ? morton_sort_records<unsigned int>(ctx, tgt->d, n, lo, inv, end_bit, cv, levels, idx->sorted, &sc)
+             : morton_sort_records<unsigned long long>(ctx, tgt->d, n, lo, inv, end_bit, cv, levels, idx->sorted, &sc);
     if (rc == PCR_OK && pcr_sync(ctx->stream) != hipSuccess) { ctx->last_error = "hipStreamSynchronize (index build)"; rc = PCR_E_HIP; }
     if (rc == PCR_OK) {
         unsigned int h_counts[PCR_MAX_LEVELS];
@@ -299,7 +305,8 @@ int pcr_grid_build(pcr_ctx* ctx, const pcr_cloud* tgt, double cell, pcr_index* i
     return rc;
 }
 
-int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell) {
+// The lay-out of a QUERY cloud: along a Hilbert curve over the cloud's own box (pcr_curve.h; PCR_QUERY_CURVE=morton: the Z curve).
+int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell, bool keep_morton) {
     if (c->morton_sorted || c->n < 2) { c->morton_sorted = true; return PCR_OK; }
     const long long n = c->n;
     double lo[3], hi[3];
@@ -311,9 +318,11 @@ int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell) {
     pcr_dev_block d_out(ctx);
     if ((rc = d_out.alloc(sizeof(pcr_pt) * n))) return rc;
     const int end_bit = pcr_morton_end_bit(lo, hi, 1.0 / cell);
+    const char* const curve_s = getenv("PCR_QUERY_CURVE");   // read per call: the tests and A/B runs switch it
+    const pcr_curve cv = pcr_curve_pick(lo, hi, 1.0 / cell, end_bit, keep_morton || (curve_s && strcmp(curve_s, "morton") == 0));
     sort_scratch sc(ctx);
-    rc = end_bit <= 32 ? morton_sort_records<unsigned int>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out.as<pcr_pt>(), &sc)
-                       : morton_sort_records<unsigned long long>(ctx, c->d, n, lo, 1.0 / cell, end_bit, 0, d_out.as<pcr_pt>(), &sc);
+    rc = end_bit <= 32 ? morton_sort_records<unsigned int>(ctx, c->d, n, lo, 1.0 / cell, end_bit, cv, 0, d_out.as<pcr_pt>(), &sc)
+                       : morton_sort_records<unsigned long long>(ctx, c->d, n, lo, 1.0 / cell, end_bit, cv, 0, d_out.as<pcr_pt>(), &sc);
     if (rc) return rc;
     pcr_dev_free(ctx, c->d);   // (the cloud's own block: a member, replaced by the sorted one)
     c->d = d_out.release<pcr_pt>();

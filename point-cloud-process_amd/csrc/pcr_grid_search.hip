@@ -1,7 +1,8 @@
 // Exact 1-NN search over the multi-level voxel-hash grid (see pcr_grid.hip for the layout).
 //
-// Queries are processed in WAVE TILES of 32 consecutive records of the Morton-sorted query cloud (a rigid transform
-// keeps a tile spatially compact, so the cloud is sorted once per pair).
+// Queries are processed in WAVE TILES of 32 consecutive records of the query cloud, which is laid out along a Hilbert curve over its own box
+// (pcr_curve.h; only the target's order has to be Morton).  A rigid transform keeps a tile spatially compact, so the cloud is sorted
+// once per pair.
 //
 //   wave tile   (wtile_search) one wave per tile, no block-level barrier: box of the cubes its queries claim (cells + 1
 //               ring at first, bound balls later; inside the ICP loop the previous pass's neighbour bounds every ball at
@@ -670,7 +671,7 @@ __device__ __forceinline__ static void wtile_search(const pcr_grid_view& gv, wti
 #endif
 }
 
-// tile index of a wave: every XCD (own L2) gets one contiguous run of the Morton-sorted queries
+// tile index of a wave: every XCD (own L2) gets one contiguous run of the curve-sorted queries
 __device__ static inline unsigned int wtile_block(int xcd_remap) {
     unsigned int blk = blockIdx.x;
     if (xcd_remap) {
@@ -1885,7 +1886,7 @@ static unsigned int wtile_point_cap(const pcr_ctx* ctx, int64_t nq) {
 constexpr unsigned int WT_BUSY_CAP = WT_PR * 48;   // staged-point cap of a tile while the queue of the last pass was long (see grid_pass_kernel)
 constexpr int WT_XCD_REMAP = 1;                     // wtile_block: one contiguous run of the sorted queries per XCD
 
-// Enqueues the search stages on `stream` over the `nq` records at `q` (a whole Morton-sorted cloud or a run of it);
+// Enqueues the search stages on `stream` over the `nq` records at `q` (a whole curve-sorted cloud or a run of it);
 // leaves res_pos (and res_d2 when the scratch has it) on the device.  `st` != null: device-resident ICP loop.
 static int grid_search_enqueue(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, int64_t nq, hipStream_t stream, const pcr_xform* x, int write_back,
                                double max_d2, bool gated, bool mark, const grid_scratch* sc, const pcr_icp_dev_state* st, bool use_prev = false) {
@@ -1910,7 +1911,7 @@ static int grid_search_enqueue(pcr_ctx* ctx, const pcr_index* idx, pcr_pt* q, in
 
 int pcr_grid_nn1(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_xform* x, double max_d2, int32_t* d_idx, double* d_d2) {
     const bool gated = (max_d2 > 0) && std::isfinite(max_d2);
-    // tiles are runs of the Morton-sorted query cloud (sorted once; rigid motion keeps them compact)
+    // tiles are runs of the curve-sorted query cloud (sorted once; rigid motion keeps them compact)
     int rc = pcr_cloud_morton_sort(ctx, qc, idx->cell);
     if (rc) return rc;
     const int64_t nq = qc->n;
@@ -2025,6 +2026,17 @@ struct loop_guard {
     ~loop_guard() { n.fetch_sub(1); }
 };
 
+bool pcr_grid_pass_fused(const pcr_index* idx, int64_t nq, const pcr_icp_params* params, double* scale, double* inv_scale, double* lin) {
+    double sc_f = 0, sc_i = 0, sc_lin = 1.0;
+    const bool gated = (params->max_d2 > 0) && std::isfinite(params->max_d2);
+    const bool fused = gated && nq <= PASS_MAX_NQ && getenv("PCR_ICP_NO_FUSED") == nullptr &&
+                       pcr_pass_fixed_scale(idx->lo, idx->hi, nq, params->max_d2, &sc_f, &sc_i, &sc_lin);
+    if (scale) *scale = sc_f;
+    if (inv_scale) *inv_scale = sc_i;
+    if (lin) *lin = sc_lin;
+    return fused;
+}
+
 int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_icp_params* params, const double T0[16],
                       pcr_icp_result* res) {
     const loop_guard in_flight(ctx->device);
@@ -2034,8 +2046,6 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     const char* const wait_s = getenv("PCR_PASS_INLINE");   // read per call: the tests switch it
     const int wait_env = wait_s ? atoi(wait_s) : -1;   // 0 / 1 force a variant; default: inline when alone on the device
     const bool gated = (params->max_d2 > 0) && std::isfinite(params->max_d2);
-    int rc = pcr_cloud_morton_sort(ctx, qc, idx->cell);
-    if (rc) return rc;
     const int64_t nq = qc->n;
     int grid = (int)((nq + 1023) / 1024);  // four queries per thread
     if (grid > ctx->cu_count) grid = ctx->cu_count;
@@ -2043,8 +2053,10 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     // bits (absurd extents keep the binary64 slabs).  Every moment is bounded by M = N * max(R^2, gate, 1), R = half diagonal of
     // the target box + gate radius.
     double sc_f = 0, sc_i = 0, sc_lin = 1.0;
-    const bool fused = gated && nq <= PASS_MAX_NQ && getenv("PCR_ICP_NO_FUSED") == nullptr &&
-                       pcr_pass_fixed_scale(idx->lo, idx->hi, nq, params->max_d2, &sc_f, &sc_i, &sc_lin);
+    const bool fused = pcr_grid_pass_fused(idx, nq, params, &sc_f, &sc_i, &sc_lin);
+    // (the binary64 slabs are added in record order: that pass keeps the Morton lay-out, and with it its bits)
+    int rc = pcr_cloud_morton_sort(ctx, qc, idx->cell, !fused);
+    if (rc) return rc;
     grid_scratch sc(ctx);
     pcr_dev_block st_blk(ctx);
     if ((rc = grid_scratch_alloc(&sc, nq, false, !fused)) || (rc = sc.prev_xyz.alloc(24 * (size_t)nq))) return rc;

@@ -147,10 +147,10 @@ int pcr_icp(pcr_ctx* ctx, pcr_cloud* source, const pcr_index* index, const pcr_i
     if (source->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
     memset(res, 0, sizeof(*res));
-    // the passes transform the source in place: lay it out first (the Morton sort may still use the box remembered from the
+    // the passes transform the source in place: lay it out first (the curve sort may still use the box remembered from the
     // upload), then forget that box
     if (index->kind == PCR_INDEX_GRID) {
-        const int rs = pcr_cloud_morton_sort(ctx, source, index->cell);
+        const int rs = pcr_cloud_morton_sort(ctx, source, index->cell, !pcr_grid_pass_fused(index, source->n, params));
         if (rs) return rs;
     }
     source->has_bbox = false;

@@ -61,7 +61,7 @@ struct pcr_grid_view {
 struct pcr_cloud {
     pcr_pt* d = nullptr;
     int64_t n = 0;
-    bool morton_sorted = false;  // records reordered for spatial locality (id keeps the caller's row)
+    bool morton_sorted = false;  // records re-laid along the query curve (pcr_curve.h: Hilbert, or Morton by switch); id keeps the caller's row
     bool has_bbox = false;       // lo/hi below are the exact bounding box of the records (computed on the host while uploading;
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};  // dropped as soon as the cloud is transformed)
 };
@@ -188,7 +188,7 @@ static inline int pcr_caught(pcr_ctx* ctx) noexcept {
 
 PCR_HIDDEN int pcr_dev_alloc(pcr_ctx* ctx, size_t bytes, void** out);
 PCR_HIDDEN void pcr_dev_free(pcr_ctx* ctx, void* p);   // (the block's capacity is the allocator's own record)
-// records of a cloud in caller row order (the device copy may be Morton-reordered)
+// records of a cloud in caller row order (the device copy may be laid out along the query curve)
 PCR_HIDDEN int pcr_cloud_rows(pcr_ctx* ctx, const pcr_cloud* c, pcr_pt* d_out);
 // the x, y, z of the records that carry the m caller rows of d_rows_sorted (ascending; repeats allowed) -> d_xyz_out[3 * d_slot[j]]
 // (d_slot null: 3 * j), whatever the order of the records: one pass over the cloud, a binary search per record (enqueued, no wait)
@@ -285,8 +285,15 @@ PCR_HIDDEN int pcr_bbox(pcr_ctx* ctx, const pcr_pt* pts, long long n, double lo[
 // bounding box of a cloud: the one remembered from the upload if still valid, otherwise a device reduction + read-back
 PCR_HIDDEN int pcr_cloud_bbox(pcr_ctx* ctx, const pcr_cloud* c, double lo[3], double hi[3]);
 PCR_HIDDEN int pcr_grid_build(pcr_ctx* ctx, const pcr_cloud* tgt, double cell, pcr_index* idx);
-// Reorder a cloud's records along a Morton curve (cell = curve resolution); rigid transforms keep the locality.
-PCR_HIDDEN int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell);
+// Reorder a QUERY cloud's records along its lay-out curve (pcr_curve.h: a Hilbert curve over the cloud's own box, the Morton curve with
+// PCR_QUERY_CURVE=morton; cell = curve resolution); rigid transforms keep the locality.  (The name is older than the curve.)
+// `keep_morton`: the Morton curve whatever the switch says -- for the ICP loop's binary64-slab pass (pcr_grid_pass_fused false),
+// whose sums follow the record order, so that it keeps adding in the order it always has.  A cloud that is laid out already stays
+// as it is.
+PCR_HIDDEN int pcr_cloud_morton_sort(pcr_ctx* ctx, pcr_cloud* c, double cell, bool keep_morton = false);
+// whether pcr_grid_icp_loop runs the one-kernel pass with fixed-point (order-independent) sums for nq queries (read per call)
+PCR_HIDDEN bool pcr_grid_pass_fused(const pcr_index* idx, int64_t nq, const pcr_icp_params* params, double* scale = nullptr, double* inv_scale = nullptr,
+                                    double* lin = nullptr);
 PCR_HIDDEN void pcr_grid_free(pcr_ctx* ctx, pcr_index* idx);
 // (the query cloud may be re-ordered on the device: record ids keep the caller's rows)
 PCR_HIDDEN int pcr_grid_nn1(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_xform* x, double max_d2, int32_t* d_idx,

@@ -281,7 +281,7 @@ int pcr_icp_point2plane(pcr_ctx* ctx, const pcr_cloud* source, const pcr_index* 
     if (source->n <= 0) return PCR_E_EMPTY;
     hipSetDevice(ctx->device);
     memset(res, 0, sizeof(*res));
-    pcr_cloud* src = const_cast<pcr_cloud*>(source);   // the search may lay the records out along a Morton curve: rows and values stay
+    pcr_cloud* src = const_cast<pcr_cloud*>(source);   // the search may lay the records out along the query curve: rows and values stay
     p2p_scratch sc(ctx);
     pcr_dev_block d_st(ctx);
     int rc;

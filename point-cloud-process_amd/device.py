@@ -158,6 +158,13 @@ class DeviceCloud:
         L.check(L.lib().pcr_cloud_download_rows(self.ctx.handle, self.handle, L.lptr(rows), len(rows), L.dptr(out)), self.ctx.handle)
         return out
 
+    def order(self):
+        """(n,) int64: the caller row of every record in device order (the identity until a grid search or `prepare` lays the
+        records out along the query curve).  A diagnostic: results never depend on the order."""
+        out = np.empty(self.n, dtype=np.int64)
+        L.check(L.lib().pcr_cloud_order(self.ctx.handle, self.handle, L.lptr(out)), self.ctx.handle)
+        return out
+
     def transform(self, T):
         T = L.as_f64(T).reshape(16)
         L.check(L.lib().pcr_cloud_transform(self.ctx.handle, self.handle, L.dptr(T)), self.ctx.handle)
