@@ -837,6 +837,50 @@ PCR_API int pcr_kitti_direction(double a, double b, double c, double* cs, double
 PCR_API int pcr_objects_kitti_boxes(pcr_ctx* ctx, const pcr_objects* objs, const pcr_kitti_calib* calib, const uint8_t* keep /* n_objects or NULL */,
                                     double* boxes /* n_objects*16 */);
 
+/* -------------------------------------------------------------- label match
+ * Training-set extraction: the per-label part of `process_sample` (Final_Project/scripts/extract.py:506-574) for ALL the KITTI 3-D
+ * labels of a frame in ONE launch (one workgroup per label) over the grouped rows of a pcr_objects handle: the rows in the label's
+ * sphere (search_radius_vector_3d, :522), moved into the label's object frame (transform_from_velo_to_obj, :116-164), those inside the
+ * label's box vote for their object (filter_by_bouding_box, :166-201), and the in-sphere rows of the winning object are the sample
+ * (:552-574).
+ *
+ * labels[16*l + ...]: 0..2 vx, vy, vz, the sphere centre in the Velodyne frame (read_label's value, `+ height/2` already added);
+ *   3 radius;  4..6 cx, cy, cz, the centre in the rectified camera frame;  7, 8 cos(ry), sin(ry) -- the CALLER takes them: no
+ *   transcendental runs on the device, as for the boxes;  9..11 length, height, width;  12..15 reserved, must be 0.
+ * Per grouped row (x, y, z), everything binary64 in exactly this order, without contraction:
+ *   dx = x - vx, dy = y - vy, dz = z - vz;   in_sphere = (dx*dx + dy*dy) + dz*dz <= radius*radius
+ *     (the library's boundary rule, as in pcr_iss and pcr_dbscan: a row exactly on the sphere is inside.  What Open3D / FLANN do at
+ *     exact equality is UNPINNED: their squared distance is accumulated in another order.)
+ *   u_i, X_i as written for the KITTI boxes above (Tr_velo_to_cam, then R0_rect; P2 is not used);   e_i = X_i - c_i
+ *   xo = cos*e_0 - sin*e_2;   yo = e_1 + height/2;   zo = sin*e_0 + cos*e_2
+ *     (R_obj_to_cam.T . e of extract.py:152-162 with its exact-zero terms dropped, then :541)
+ *   in_box = -length/2 <= xo <= length/2 && -height/2 <= yo <= height/2 && -width/2 <= zo <= width/2   (both faces inclusive,
+ *     extract.py:184-190)
+ * Per label:
+ *   k = the rows with in_sphere, over all objects;   votes[o] = the rows of object o with in_sphere && in_box;
+ *   winner = the LOWEST o with the largest votes[o] > 0 (np.unique ascends and max(..., key) keeps the first maximum, :196-199);
+ *     -1 when no row is in the box (`return None`, :192);
+ *   the selected rows = the rows of the winner with in_sphere -- not in_box (:552);  n_sel their count;
+ *   centre_a = S(selected coordinate a) / (double)n_sel, S the object sum of the KITTI boxes restricted to the selected rows:
+ *     position p = 0 .. count-1 within the winner belongs to lane p % 64; p_l starts from +0.0 and adds its SELECTED rows in
+ *     ascending p (a skipped row adds nothing); then p_l += p_{l+s} for every l < s, s = 32, 16, 8, 4, 2, 1; the sum is p_0.  This
+ *     order belongs to the ABI, not to the launch shape.
+ * result[8*l + ...]: 0 k;  1 winner or -1.0;  2 votes[winner];  3 n_sel;  4..6 centre;  7 +0.0.  Without a winner entries 2 and 3 are
+ *   0.0 and entries 4..6 are NaN.
+ * sel_bits (may be NULL): bit p % 64 of word l*words + p/64 is set iff position p of the winner is selected; every word of the
+ *   L*words block is written, those beyond the winner's count (all of them without a winner) with zero.  `words` must be at least
+ *   ceil(max object count / 64): PCR_E_INVALID otherwise.
+ * An object whose stored box (pcr_objects_stats) cannot meet the sphere is not read; the test is made in the arithmetic of in_sphere
+ *   itself, whose every step is monotone, so it never changes k, the votes or any bit of the output.
+ * PCR_E_INVALID, before any launch: objs, calib, labels (with L > 0) or result NULL; a calibration entry (R0_rect, Tr_velo_to_cam, P2: the
+ *   struct is checked as for the boxes) or a label entry 0..11 that is not finite; a negative radius or dimension; a reserved entry that is not zero; L < 0.  L == 0: PCR_OK.  A handle
+ *   without labelled rows: PCR_OK, every label gets k = 0, winner = -1, and nothing is launched.  The call returns after the
+ *   context's stream has drained.                                                                                               */
+#define PCR_LABEL_DOUBLES 16
+#define PCR_LABEL_RESULT_DOUBLES 8
+PCR_API int pcr_objects_match_labels(pcr_ctx* ctx, const pcr_objects* objs, const pcr_kitti_calib* calib, const double* labels /* L*16, host */, int64_t L,
+                                     double* result /* L*8, host */, uint64_t* sel_bits /* L*words, host, or NULL */, int64_t words);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

@@ -67,6 +67,20 @@ from .detection import (  # noqa: F401
     transform_to_cam,
     transform_to_pixel,
 )
+from . import extract  # noqa: F401
+from .extract import (  # noqa: F401
+    add_label,
+    filter_by_bouding_box,
+    get_object_category,
+    get_object_pcd_df,
+    init_label,
+    label_records,
+    match_labels,
+    process_sample,
+    read_label,
+    transform_from_cam_to_velo,
+    transform_from_velo_to_obj,
+)
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
 from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401

@@ -40,6 +40,8 @@ PCR_SPECTRAL_MAX_NNK = 15
 PCR_OBJECTS_TILE = 128
 PCR_KITTI_BOX_DOUBLES = 16
 PCR_KITTI_LDS_ROWS = 512
+PCR_LABEL_DOUBLES = 16
+PCR_LABEL_RESULT_DOUBLES = 8
 
 
 class IcpParams(C.Structure):
@@ -380,6 +382,8 @@ SIGNATURES = {
     # KITTI boxes: the direction rule on the host, and (ctx, objects handle, calibration, keep flags, n_objects x 16 doubles)
     "pcr_kitti_direction": (C.c_int, [C.c_double, C.c_double, C.c_double, _dp, _dp]),
     "pcr_objects_kitti_boxes": (C.c_int, [_vp, _vp, C.POINTER(KittiCalib), C.POINTER(C.c_uint8), _dp]),
+    # label match: (ctx, objects handle, calibration, L x 16 label doubles, L, L x 8 result doubles, L x words ballot words or NULL, words)
+    "pcr_objects_match_labels": (C.c_int, [_vp, _vp, C.POINTER(KittiCalib), _dp, C.c_int64, _dp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),

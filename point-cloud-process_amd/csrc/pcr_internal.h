@@ -90,6 +90,17 @@ struct pcr_index {
     int32_t* row_pos = nullptr;
 };
 
+// object batches (pcr_objects.hip builds it; pcr_label_match.hip reads it)
+struct pcr_objects {
+    int64_t n = 0;           // rows of the cloud the labels belong to
+    int64_t n_objects = 0;
+    int64_t m = 0;           // labelled rows
+    pcr_pt* recs = nullptr;        // [m] labelled records object by object, ascending caller row (id) within each
+    long long* d_off = nullptr;    // [n_objects + 1]
+    double* d_stats = nullptr;     // [n_objects][9]: mean, min, max
+    std::vector<int64_t> off;      // the offsets on the host
+};
+
 struct pcr_ctx {
     int device = 0;
     hipStream_t stream = nullptr;

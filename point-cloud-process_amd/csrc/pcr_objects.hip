@@ -26,18 +26,9 @@
 #include <limits>
 #include <vector>
 #include "pcr_internal.h"
+#include "pcr_kitti_dev.h"
 #include "pcr_sort.h"
 #include "pcr_wave.h"
-
-struct pcr_objects {
-    int64_t n = 0;           // rows of the cloud the labels belong to
-    int64_t n_objects = 0;
-    int64_t m = 0;           // labelled rows
-    pcr_pt* recs = nullptr;        // [m] labelled records object by object, ascending caller row (id) within each
-    long long* d_off = nullptr;    // [n_objects + 1]
-    double* d_stats = nullptr;     // [n_objects][9]: mean, min, max
-    std::vector<int64_t> off;      // the offsets on the host
-};
 
 namespace {
 
@@ -202,8 +193,6 @@ objects_pack_kernel(const pcr_pt* __restrict__ recs, const long long* __restrict
 constexpr int KB_ROWS = PCR_KITTI_LDS_ROWS;
 static_assert(KB_ROWS % OB_WAVE == 0 && 3 * KB_ROWS * sizeof(double) <= 64 * 1024, "the camera-frame rows of one object, a whole number of wave loads");
 
-struct kb_calib { double T[12], R0[9], P[12]; };   // row-major: Tr_velo_to_cam, R0_rect, P2
-
 // The heading direction of the x-z covariance [[a, b], [b, c]] as detect.py:47-54 reads it off np.linalg.eig (include/pcr.h has the
 // derivation).  One source for pcr_kitti_direction and for the kernel.
 __host__ __device__ inline void kitti_direction_rule(double a, double b, double c, double* cs, double* sn) {
@@ -220,23 +209,6 @@ __host__ __device__ inline void kitti_direction_rule(double a, double b, double 
     const double len = sqrt(e0 * e0 + e1 * e1);
     *cs = e0 / len;
     *sn = e1 / len;
-}
-
-// transform_to_cam (transform_coords_utils.py:4-32) of one row
-__device__ static inline void kb_cam(const kb_calib& k, const pcr_pt& r, double (&X)[3]) {
-    double u[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u[i] = ((k.T[4 * i] * r.x + k.T[4 * i + 1] * r.y) + k.T[4 * i + 2] * r.z) + k.T[4 * i + 3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) X[i] = (k.R0[3 * i] * u[0] + k.R0[3 * i + 1] * u[1]) + k.R0[3 * i + 2] * u[2];
-}
-
-// The object sum of include/pcr.h: lane l holds the sum of rows l, l + 64, ...; p_l += p_{l+s} for l < s, s = 32 .. 1; p_0 to every lane.
-// (A lane >= s adds something it never hands on: at step s only lanes below 2s are read.)
-__device__ static inline double kb_total(double p) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) p += __shfl_down(p, s, OB_WAVE);
-    return readlane_f64(p, 0);
 }
 
 // One wave per object.  Rows go to lanes round robin (row j to lane j % 64), so every sum has the order of include/pcr.h whatever
@@ -276,7 +248,7 @@ kitti_boxes_kernel(const pcr_pt* __restrict__ recs, const long long* __restrict_
     }
     double ctr[3];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) ctr[i] = kb_total(sum[i]) / n;
+    for (int i = 0; i < 3; ++i) ctr[i] = wave_object_sum_f64(sum[i]) / n;
     const double left = wave_min_f64(mn[0]), top = wave_min_f64(mn[1]), right = -wave_min_f64(ng[0]), bottom = -wave_min_f64(ng[1]);
 
     // pass 2: centred x-z moments, then the direction in every lane
@@ -288,7 +260,7 @@ kitti_boxes_kernel(const pcr_pt* __restrict__ recs, const long long* __restrict_
         const double d0 = X[0] - ctr[0], d2 = X[2] - ctr[2];
         m[0] += d0 * d0; m[1] += d0 * d2; m[2] += d2 * d2;
     }
-    const double a = kb_total(m[0]) / n, b = kb_total(m[1]) / n, c = kb_total(m[2]) / n;
+    const double a = wave_object_sum_f64(m[0]) / n, b = wave_object_sum_f64(m[1]) / n, c = wave_object_sum_f64(m[2]) / n;
     double cs, sn;
     kitti_direction_rule(a, b, c, &cs, &sn);
     const double ms = -sn;   // sin(-ry)

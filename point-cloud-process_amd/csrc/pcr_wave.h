@@ -109,6 +109,15 @@ __device__ static inline double readlane_f64(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
+// The tree of the object sum of include/pcr.h ("KITTI boxes", "label match"): lane l holds the sum of its rows l, l + 64, ...;
+// p_l += p_{l+s} for l < s, s = 32 .. 1; p_0 to every lane.  (A lane >= s adds something it never hands on: at step s only lanes
+// below 2s are read.)  All 64 lanes must be active.
+__device__ static inline double wave_object_sum_f64(double p) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) p += __shfl_down(p, s, 64);
+    return readlane_f64(p, 0);
+}
+
 // LDS hand-off between the lanes of ONE wave: LDS operations of a wave execute in order, so no hardware wait is
 // needed, but the compiler must neither forward a lane's own earlier store to its load nor move accesses across
 __device__ static inline void wave_sync() {

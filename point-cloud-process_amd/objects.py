@@ -58,6 +58,7 @@ class ObjectBatch:
         self.offsets = np.zeros(n_objects + 1, dtype=np.int64)
         L.check(L.lib().pcr_objects_offsets(self.handle, L.lptr(self.offsets)), ctx.handle)
         self.m = int(self.offsets[-1])
+        self._grouped_rows = None
 
     @property
     def handle(self):
@@ -118,6 +119,33 @@ class ObjectBatch:
             kp = keep.ctypes.data_as(_u8p)
         L.check(L.lib().pcr_objects_kitti_boxes(self.ctx.handle, self.handle, C.byref(cal), kp, L.dptr(boxes)), self.ctx.handle)
         return boxes
+
+    def match_labels(self, calib, labels):
+        """pcr_objects_match_labels (include/pcr.h, "label match") for `labels`, an (L,16) array of label records -> dict with one
+        entry per label: ``k`` rows of any object in the label's sphere, ``object_id`` the object with the most rows in the label's
+        box (the lowest id on a tie, -1: none), ``votes`` its rows in the box, ``count`` its rows in the sphere (the selected rows),
+        ``center`` (L,3) their centre (NaN without an object), ``positions`` a list of int64 arrays, the places of the selected rows
+        within the object in ascending caller row, unpacked from the ballot words, ``rows`` their caller rows."""
+        rec = np.ascontiguousarray(labels, dtype=np.float64)
+        if rec.ndim != 2 or rec.shape[1] != L.PCR_LABEL_DOUBLES:
+            raise ValueError(f"expected (L, {L.PCR_LABEL_DOUBLES}) label records, got shape {rec.shape}")
+        n = rec.shape[0]
+        cal = calib_struct(calib)
+        counts = np.diff(self.offsets)
+        words = max(int(-(-int(counts.max()) // 64)) if len(counts) else 0, 1)
+        result = np.zeros((n, L.PCR_LABEL_RESULT_DOUBLES), dtype=np.float64)
+        bits = np.zeros((n, words), dtype=np.uint64)
+        L.check(L.lib().pcr_objects_match_labels(self.ctx.handle, self.handle, C.byref(cal), L.dptr(rec), n, L.dptr(result),
+                                                 bits.ctypes.data_as(C.POINTER(C.c_uint64)), words), self.ctx.handle)
+        object_id = result[:, 1].astype(np.int64)
+        unpacked = np.unpackbits(bits.view(np.uint8), axis=1, bitorder="little")   # (the words are little-endian on every host of a gfx950)
+        positions = [np.flatnonzero(row).astype(np.int64) for row in unpacked]
+        if self._grouped_rows is None and (object_id >= 0).any():
+            self._grouped_rows = self.rows().astype(np.int64)   # (the handle never changes: one read-back serves every later call)
+        grouped = self._grouped_rows
+        rows = [grouped[self.offsets[o] + p] if o >= 0 else np.zeros(0, dtype=np.int64) for o, p in zip(object_id, positions)]
+        return {"k": result[:, 0].astype(np.int64), "object_id": object_id, "votes": result[:, 2].astype(np.int64), "count": result[:, 3].astype(np.int64),
+                "center": result[:, 4:7].copy(), "positions": positions, "rows": rows}
 
     def free(self):
         if self._h:
