@@ -713,6 +713,43 @@ PCR_API int pcr_pn2_gather_points(void* stream, int b, int c, int n, int npoints
 PCR_API int pcr_pn2_group_points(void* stream, int b, int c, int n, int npoints, int nsample, const float* points /* b,c,n */,
                                  const int32_t* idx /* b,npoints,nsample */, float* out /* b,c,npoints,nsample */);
 
+/* ------------------------------------------- PointNet++ gradients
+ * The gradients of gather, group and three_interpolate with respect to their features (the reference's gather_points_grad,
+ * group_points_grad and three_interpolate_grad, called from pointnet2_utils.py:93-99, :217-237 and :164-189; its kernels add with
+ * atomicAdd, in no order).  Same calling rules as the ops above: caller's device memory, caller's stream, no context, no allocation,
+ * no host synchronisation.  All three are the transpose of a gather along the last axis.  With k slots per cloud and
+ * idx[b, slot] in [0, n):
+ *   grad_points[b, c, i] = sum of term[b, c, slot] over the slots with idx[b, slot] == i, in ASCENDING slot order: the accumulator
+ *   starts at +0.0f and takes one rounded binary32 addition per term; a point that no slot names gets +0.0f.
+ *   gather:            k = npoints,          term = grad_out[b, c, slot]
+ *   group:             k = npoints*nsample,  slot = j*nsample + s,  term = grad_out[b, c, j, s]
+ *   three_interpolate: k = 3*n,              slot = 3*j + kk,       term = grad_out[b, c, j] * weight[b, j, kk], rounded once (no
+ *                      fused multiply-add), then added; here the points are the m known ones.
+ * This is what np.add.at(out, idx, term) does on a float32 array, so the result is the same bits on every run and on the host.  No
+ * floating-point atomics are used.  Infinities follow the same additions; the sign and payload of a NaN they produce are not
+ * part of the contract.
+ *
+ * The inverse index says, per point, which slots name it: start (b, n + 1) and slots (b, k), point i of cloud bi owning
+ * slots[bi, start[bi, i] .. start[bi, i+1]) in ascending order; start[bi, 0] = 0, start[bi, n] = k.  It is a function of idx alone,
+ * is built once per index tensor (pcr_pn2_inverse_index, a stable radix sort of the pairs (bi*n + idx, slot) on the caller's
+ * stream) and serves every channel and every tensor that was gathered with that idx.  Its workspace of
+ * pcr_pn2_inverse_index_bytes(b, n, k) bytes is the caller's, 256-byte aligned, and free again once the stream has passed the
+ * call.  The query returns the size (0 for an empty problem) or a negative PCR_E_* code.
+ * Status: PCR_E_INVALID for a negative size, a NULL pointer where data is needed, n == 0 with slots to place, a workspace that is
+ * misaligned or too small; PCR_E_UNSUPPORTED for b*n > 2^32 (the sort's keys), k > 2^31 - 1, or more than 65 535 clouds or channel
+ * tiles; PCR_E_HIP for a failed launch.  b == 0, c == 0 or no points: PCR_OK, nothing is launched.  k == 0 with points: start is
+ * zeroed, grad_points is zeroed.  Entries of idx are assumed in range, as for the forward ops.                                   */
+PCR_API long long pcr_pn2_inverse_index_bytes(int b, int n, int k);
+PCR_API int pcr_pn2_inverse_index(void* stream, int b, int n, int k, const int32_t* idx /* b,k */, void* workspace, long long workspace_bytes,
+                                  int32_t* start_out /* b,n+1 */, int32_t* slots_out /* b,k */);
+PCR_API int pcr_pn2_gather_points_grad(void* stream, int b, int c, int n, int npoints, const float* grad_out /* b,c,npoints */,
+                                       const int32_t* start /* b,n+1 */, const int32_t* slots /* b,npoints */, float* grad_points /* b,c,n */);
+PCR_API int pcr_pn2_group_points_grad(void* stream, int b, int c, int n, int npoints, int nsample, const float* grad_out /* b,c,npoints,nsample */,
+                                      const int32_t* start /* b,n+1 */, const int32_t* slots /* b,npoints*nsample */, float* grad_points /* b,c,n */);
+PCR_API int pcr_pn2_three_interpolate_grad(void* stream, int b, int c, int n, int m, const float* grad_out /* b,c,n */,
+                                           const int32_t* start /* b,m+1 */, const int32_t* slots /* b,3*n */, const float* weight /* b,n,3 */,
+                                           float* grad_points /* b,c,m */);
+
 /* Set abstraction for inference, fused: gather, shared MLP (batch norm folded into the weights by the caller), ReLU and the maximum
  * over the ball in one kernel; the grouped tensor (b, C, m, nsample) is never stored.  Same calling rules as the ops above.  `widths`,
  * `weights` and `biases` are HOST arrays of n_layers entries (read during the call); weights[l] and biases[l] are device pointers,

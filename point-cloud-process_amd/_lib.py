@@ -367,6 +367,12 @@ SIGNATURES = {
     "pcr_pn2_three_interpolate": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "pcr_pn2_gather_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "pcr_pn2_group_points": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    # the gradients in a fixed order: the inverse index of an index tensor (workspace size, build), then the three sums over it
+    "pcr_pn2_inverse_index_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "pcr_pn2_inverse_index": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_longlong, _vp, _vp]),
+    "pcr_pn2_gather_points_grad": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "pcr_pn2_group_points_grad": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "pcr_pn2_three_interpolate_grad": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     # (stream, b, n, m, nsample, c_feat, use_xyz, xyz, new_xyz, feats, idx, n_layers, host widths, host weight / bias pointer arrays, out, stride)
     "pcr_pn2_sa_mlp_max": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, C.c_longlong]),

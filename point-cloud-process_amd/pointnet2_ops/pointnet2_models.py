@@ -1,7 +1,7 @@
 """The reference's two classifiers (Final_Project/pointnet2/models/pointnet2_ssg_cls.py and pointnet2_msg_cls.py) as plain
 ``nn.Module``s over ``pointnet2_modules``: the same layer specifications, sub-module names and order (``SA_modules.<i>...``,
 ``fc_layer.<i>``), so the ``model_state`` of the reference's checkpoint loads with ``load_state_dict``.  The training loop of the
-reference's classes (a pytorch_lightning module) is not part of them.
+reference's classes (a pytorch_lightning module) is not part of them; the reference's ``train.py`` is ``pointnet2_train``.
 """
 from __future__ import annotations
 

@@ -5,10 +5,17 @@ the same names and signatures, torch tensors on the device in and out, the six f
 Every argument is checked before anything is launched and a bad one raises ValueError: dtype (float32 data, int32 indices), rank,
 contiguity, matching batch sizes, and that the tensors live on a GPU.  There is no host path.
 
-The three gradients (gather, group, interpolate) are composed from torch's ``scatter_add_`` on the device, so training works; their
-summation order is torch's (floating-point atomics), not a fixed one.
+The three gradients (gather, group, interpolate) have two paths.  By default they are composed from torch's ``scatter_add_`` on the
+device; their summation order is then torch's (floating-point atomics), not a fixed one.  Under ``fixed_order_gradients()`` (or after
+``set_fixed_order_gradients(True)``) they are HIP kernels with a written order (include/pcr.h, "PointNet++ gradients"): per output
+the terms are added one by one in ascending slot order, so two runs give the same bits, NumPy's ``np.add.at`` on float32 gives the
+same bits, and nothing in them depends on ``torch.use_deterministic_algorithms``.  The switch is read in ``forward`` and remembered
+for that call's ``backward``.  ``inverse_index`` and ``scatter_rows_ordered`` are the two steps for direct use; the inverse index is
+kept on the ``idx`` tensor object (guarded by its ``_version`` and the stream), so tensors grouped with the same ``idx`` share one build.
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 import torch
@@ -100,6 +107,93 @@ def _scatter_rows(grad_cols, idx_cols, n):
     return out.scatter_add_(2, idx_cols.to(torch.int64).view(B, 1, K).expand(B, C, K), grad_cols)
 
 
+# ---------------------------------------------------------------- the gradients in a fixed order
+_fixed_order = False
+
+
+def set_fixed_order_gradients(enabled):
+    """Switch the gradients of gather / group / three_interpolate to the fixed-order kernels (True) or back to torch's
+    ``scatter_add_`` (False, the default) for every later ``forward``; returns the previous setting."""
+    global _fixed_order
+    previous, _fixed_order = _fixed_order, bool(enabled)
+    return previous
+
+
+def fixed_order_gradients_enabled():
+    return _fixed_order
+
+
+@contextlib.contextmanager
+def fixed_order_gradients(enabled=True):
+    """Context manager around ``set_fixed_order_gradients``: a ``forward`` inside it decides its own ``backward``, wherever that runs."""
+    previous = set_fixed_order_gradients(enabled)
+    try:
+        yield
+    finally:
+        set_fixed_order_gradients(previous)
+
+
+def inverse_index(idx, n):
+    """idx (B, ...) int32 with entries in [0, n), its trailing axes flattened to K slots per cloud -> (start (B, n + 1), slots (B, K))
+    int32: point i of cloud b is named by slots[b, start[b, i]:start[b, i + 1]], ascending (include/pcr.h, pcr_pn2_inverse_index).
+    Built on the current stream and kept on the ``idx`` object; reused while ``idx._version``, its address, n and the current
+    stream are unchanged (a call on another stream builds its own, so no stream reads an index that another is still writing).
+    ``_version`` sees torch's in-place operations only: after writing into ``idx`` through its raw address, drop the attribute
+    ``idx._pcr_inverse_index``."""
+    rank = idx.dim() if isinstance(idx, torch.Tensor) and idx.dim() == 3 else 2
+    _check((idx, "idx", i32, ("B",) + (None,) * (rank - 1)))
+    n = _count(n, "n")
+    B = idx.shape[0]
+    K = _count(int(np.prod(idx.shape[1:])), "the number of slots per cloud")
+    if n == 0 and B and K:
+        raise ValueError("idx names points of a cloud without points")
+    try:
+        version = idx._version
+    except RuntimeError:     # tensors made in inference mode keep no version: build every time
+        version = None
+    key = (version, n, idx.data_ptr(), torch.cuda.current_stream(idx.device).cuda_stream)
+    kept = getattr(idx, "_pcr_inverse_index", None)
+    if kept is not None and version is not None and kept[0] == key:
+        return kept[1], kept[2]
+    start = torch.empty((B, n + 1), dtype=i32, device=idx.device)
+    slots = torch.empty((B, K), dtype=i32, device=idx.device)
+    with torch.cuda.device(idx.device):
+        need = _lib.lib().pcr_pn2_inverse_index_bytes(B, n, K)
+        if need < 0:
+            _lib.check(int(need))
+        work = torch.empty((int(need),), dtype=torch.uint8, device=idx.device)
+    _launch(idx, "pcr_pn2_inverse_index", B, n, K, idx.data_ptr(), work.data_ptr(), int(need), start.data_ptr(), slots.data_ptr())
+    if version is not None:
+        idx._pcr_inverse_index = (key, start, slots)
+    return start, slots
+
+
+def scatter_rows_ordered(grad, idx, n, weight=None):
+    """The transpose of a gather along the last axis in the written order of include/pcr.h ("PointNet++ gradients"):
+    out[b, c, i] = the terms of the slots with idx[b, slot] == i, added in ascending slot order in float32 -> (B, C, n).
+
+    grad (B, C, K) with idx (B, K): gather's gradient.  grad (B, C, npoint, nsample) with idx (B, npoint, nsample): group's.
+    grad (B, C, m) with idx and weight (B, m, 3): three_interpolate's, term = grad[b, c, j] * weight[b, j, k] rounded once."""
+    if weight is not None:
+        _check((grad, "grad", f32, ("B", None, "j")), (idx, "idx", i32, ("B", "j", 3)), (weight, "weight", f32, ("B", "j", 3)))
+    elif isinstance(idx, torch.Tensor) and idx.dim() == 3:
+        _check((grad, "grad", f32, ("B", None, "j", "s")), (idx, "idx", i32, ("B", "j", "s")))
+    else:
+        _check((grad, "grad", f32, ("B", None, "j")), (idx, "idx", i32, ("B", "j")))
+    n = _count(n, "n")
+    B, C = grad.shape[:2]
+    start, slots = inverse_index(idx, n)
+    out = torch.empty((B, C, n), dtype=f32, device=grad.device)
+    if weight is not None:
+        _launch(grad, "pcr_pn2_three_interpolate_grad", B, C, grad.shape[2], n, grad.data_ptr(), start.data_ptr(), slots.data_ptr(),
+                weight.data_ptr(), out.data_ptr())
+    elif idx.dim() == 3:
+        _launch(grad, "pcr_pn2_group_points_grad", B, C, n, idx.shape[1], idx.shape[2], grad.data_ptr(), start.data_ptr(), slots.data_ptr(), out.data_ptr())
+    else:
+        _launch(grad, "pcr_pn2_gather_points_grad", B, C, n, idx.shape[1], grad.data_ptr(), start.data_ptr(), slots.data_ptr(), out.data_ptr())
+    return out
+
+
 class GatherOperation(Function):
     @staticmethod
     def forward(ctx, features, idx):
@@ -113,11 +207,14 @@ class GatherOperation(Function):
         _launch(features, "pcr_pn2_gather_points", B, C, N, npoint, features.data_ptr(), idx.data_ptr(), out.data_ptr())
         ctx.save_for_backward(idx)
         ctx.n = N
+        ctx.fixed_order = _fixed_order
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
+        if ctx.fixed_order:
+            return scatter_rows_ordered(grad_out.contiguous(), idx, ctx.n), None
         return _scatter_rows(grad_out.contiguous(), idx, ctx.n), None
 
 
@@ -168,12 +265,15 @@ class ThreeInterpolate(Function):
         _launch(features, "pcr_pn2_three_interpolate", B, c, m, n, features.data_ptr(), idx.data_ptr(), weight.data_ptr(), out.data_ptr())
         ctx.save_for_backward(idx, weight)
         ctx.m = m
+        ctx.fixed_order = _fixed_order
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         """Gradient of the features only (as in the reference, the weights get none)."""
         idx, weight = ctx.saved_tensors
+        if ctx.fixed_order:
+            return scatter_rows_ordered(grad_out.contiguous(), idx, ctx.m, weight=weight), None, None
         B, c, n = grad_out.shape
         terms = (grad_out.unsqueeze(-1) * weight.unsqueeze(1)).reshape(B, c, 3 * n)
         return _scatter_rows(terms, idx.reshape(B, 3 * n), ctx.m), None, None
@@ -195,11 +295,14 @@ class GroupingOperation(Function):
         _launch(features, "pcr_pn2_group_points", B, C, N, npoint, nsample, features.data_ptr(), idx.data_ptr(), out.data_ptr())
         ctx.save_for_backward(idx)
         ctx.n = N
+        ctx.fixed_order = _fixed_order
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         (idx,) = ctx.saved_tensors
+        if ctx.fixed_order:
+            return scatter_rows_ordered(grad_out.contiguous(), idx, ctx.n), None
         B, C = grad_out.shape[:2]
         return _scatter_rows(grad_out.reshape(B, C, -1), idx.reshape(B, -1), ctx.n), None
 
