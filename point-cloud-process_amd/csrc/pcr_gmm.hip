@@ -385,7 +385,7 @@ void state_to_host(const gmm_state* h, int k, int dim, double* means, double* co
 int gmm_begin(pcr_stream_fit* r, const pcr_cloud* cloud, int k, int dim, const gmm_state* h) {
     pcr_ctx* ctx = r->ctx;
     int rc;
-    if ((rc = pcr_stream_begin(r, cloud, k, dim, GM_TILE, PCR_CW_GMM_TICKET, h, sizeof(gmm_state), GM_NSUM_MAX))) return rc;
+    if ((rc = pcr_stream_begin(r, cloud->d, cloud->n, k, dim, GM_TILE, PCR_CW_GMM_TICKET, h, sizeof(gmm_state), GM_NSUM_MAX))) return rc;
     hipLaunchKernelGGL(gmm_init_kernel, dim3(1), dim3(64), 0, ctx->stream, r->st.as<gmm_state>(), k, dim);
     PCR_HIP(ctx, hipGetLastError());
     return PCR_OK;

@@ -1,203 +1,65 @@
 // K-Means clustering (Lloyd's iteration): class K_Means of Cluster_KMeans_GMM/compare_cluster.py:16,105,164-170 on a device-resident
 // cloud.  The reference's KMeans.py is not in its tree; the semantics are the ones include/pcr.h states.
 //
-// One streaming pass over the 32-byte records per iteration:
-//   kmeans_assign_kernel  label = argmin_k d2 under the CURRENT centres (direct form, lowest k on ties), per cluster the exact count
-//                         N_k and S_k = sum x, and the inertia of the current centres.  The block that takes the last ticket divides,
-//                         keeps the centre of an empty cluster, applies the stop rule, writes the next centres and the history entries;
-//   kmeans_label_kernel   the final pass and predict: labels by caller row, counts and inertia under the given centres.
-// Centres are broadcast from LDS.  A lane keeps KM_PTS points and their labels in registers; clusters go by in chunks whose masked
-// accumulators (label == k ? x : 0) stay in registers, so the order of every sum is fixed.
-// Sums: per lane over its points in order, wave totals on the DPP network, a fixed tree over the block's four waves, one slab per block
-// in ctx->d_partials, and the last block adds the slabs in a fixed order.  Counts are integers all the way (a slab's count slots hold
-// 64-bit integers).  No floating-point atomics, the block count depends on n alone: two runs give the same bits.  Loop state lives on
-// the device; passes enqueued behind a stop are no-ops, and the host reads a 40-byte head once per KM_ITERS_PER_SYNC iterations.
+// One streaming pass over the 32-byte records per iteration: the Lloyd pass of pcr_lloyd.h on a cloud source, KM_PTS points per lane.
+//   kmeans_assign_kernel  lloyd_assign; the last block also leaves S_k in the state and the two history entries;
+//   kmeans_label_kernel   lloyd_label: the final pass and predict, labels by caller row.
+// Passes enqueued behind a stop are no-ops; the host reads the state's 40-byte head once per LLOYD_ITERS_PER_SYNC iterations.
 #include <cmath>
 #include <cstring>
 #include <vector>
 #include "pcr_internal.h"
+#include "pcr_lloyd.h"
 #include "pcr_stream_fit.h"
-#include "pcr_wave.h"
 
 namespace {
 
 constexpr int KM_MAX_K = PCR_KMEANS_MAX_K;
-constexpr int KM_BLOCK = PCR_STREAM_BLOCK;
 constexpr int KM_PTS = 4;                        // points per lane, in registers while the clusters go by
-constexpr int KM_TILE = KM_PTS * KM_BLOCK;       // points per block: the block count is ceil(n / KM_TILE)
-constexpr int KM_CHUNK = 8;                      // clusters per chunk: 8 x dim sums and 8 counts per lane
-constexpr int KM_NSUM_MAX = KM_MAX_K * 4 + 1;    // values per block slab: K * (1 + dim) + 1
-constexpr int KM_ITERS_PER_SYNC = 8;             // iterations enqueued per read-back of the loop state's head
 
-// Loop state on the device.  The head (the first 40 bytes) is what the host reads per chunk of iterations.
-struct __attribute__((aligned(16))) km_state {
-    int it;              // completed iterations
-    int stop;            // no further assign pass may run
-    int converged;       // stopped by shift <= tol
-    int n_empty;         // clusters without points in the last pass that counted
-    int max_iter, pad;
-    double inertia;      // of the centres the last pass assigned under
-    double shift;        // max_k |c_new[k] - c_old[k]| of the last update
-    double tol;
-    double c[KM_MAX_K * 3];        // current centres
-    double sums[KM_MAX_K * 3];     // S_k of the last assign pass
-    long long counts[KM_MAX_K];    // N_k of the last pass
+// The records of a cloud, dim 2 or 3: tiles of KM_PTS * 256 points, labels by CALLER row (Morton-reordered records: id is the row)
+template <int DIM>
+struct km_cloud_source {
+    using rec = pcr_pt;
+    static constexpr int KMAX = KM_MAX_K, CSTRIDE = 3, PTS = KM_PTS, DMAX = DIM;
+    static constexpr int CHUNK = 8;                  // clusters per chunk: 8 x dim sums and 8 counts per lane
+    static constexpr int NSUM = KM_MAX_K * 4 + 1;    // values per block slab: K * (1 + dim) + 1
+    __device__ static constexpr int dims(int) { return DIM; }
+    __device__ static void load(const pcr_pt* __restrict__ pts, long long n, int, double (&v)[PTS][DMAX], bool (&valid)[PTS], long long (&row)[PTS]) {
+        double x[PTS], y[PTS], z[PTS];
+        block_tile_load<PTS, true>(pts, n, x, y, z, valid, row);
+#pragma unroll
+        for (int p = 0; p < PTS; ++p) { v[p][0] = x[p]; v[p][1] = y[p]; if (DIM == 3) v[p][DIM - 1] = z[p]; }
+    }
 };
-constexpr size_t KM_HEAD_BYTES = offsetof(km_state, tol);
-static_assert(KM_HEAD_BYTES == 40, "head of the loop state");
+constexpr int KM_TILE = KM_PTS * PCR_STREAM_BLOCK;
+constexpr int KM_NSUM_MAX = km_cloud_source<3>::NSUM;
+
+struct km_state : lloyd_state<KM_MAX_K, 3> {
+    double sums[KM_MAX_K * 3];     // S_k of the last assign pass
+};
 static_assert(sizeof(km_state) <= PCR_SMALL_D2H_BYTES && sizeof(km_state) % 8 == 0, "state read back through pcr_d2h_small");
 
-// squared distance in the direct form, the order of np.sum over (dx^2, dy^2, dz^2)
 template <int DIM>
-__device__ inline double km_d2(const double* c, double x, double y, double z) {
-    const double dx = x - c[0], dy = y - c[1];
-    double d = dx * dx + dy * dy;
-    if (DIM == 3) { const double dz = z - c[2]; d = d + dz * dz; }
-    return d;
-}
-
-// block_slab_sums (pcr_wave.h) with integer adds in the count slots (t < K * nt with t % nt == 0), binary64 adds elsewhere
-__device__ inline bool km_block_sums(const double (*s_part)[KM_NSUM_MAX], int nsum, int K, int nt, double* __restrict__ partials,
-                                     unsigned int* __restrict__ ticket, double (*s_red)[KM_NSUM_MAX], double* s_tot) {
-    return block_slab_sums<KM_NSUM_MAX>(s_part, nsum, partials, ticket, s_red, s_tot, [K, nt](double x, double y, int t) {
-        const bool count = t < K * nt && t % nt == 0;
-        return count ? __longlong_as_double(__double_as_longlong(x) + __double_as_longlong(y)) : x + y;
-    });
-}
-
-// The block's tile under the centres of `st`: labels (by caller row, if asked for), and per wave in s_part the cluster values
-// (SUMS: N_k, S_k at [k * (1 + DIM), ...); else N_k at [k]) and the inertia behind them.
-template <int DIM, bool SUMS>
-__device__ inline void km_tile_pass(const pcr_pt* __restrict__ pts, long long n, int K, const km_state* __restrict__ st, int* __restrict__ labels,
-                                    double* s_c, double (*s_part)[KM_NSUM_MAX]) {
-    constexpr int NT = SUMS ? 1 + DIM : 1;
-    for (int t = threadIdx.x; t < K * 3; t += KM_BLOCK) s_c[t] = st->c[t];
-    double x[KM_PTS], y[KM_PTS], z[KM_PTS];
-    int lab[KM_PTS];
-    long long id[KM_PTS];
-    bool valid[KM_PTS];
-    block_tile_load<KM_PTS, true>(pts, n, x, y, z, valid, id);
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    double inertia = 0.0;
-#pragma unroll
-    for (int p = 0; p < KM_PTS; ++p) {
-        double best = km_d2<DIM>(s_c, x[p], y[p], z[p]);
-        int arg = 0;
-        for (int k = 1; k < K; ++k) {
-            const double d = km_d2<DIM>(s_c + 3 * k, x[p], y[p], z[p]);
-            if (d < best) { best = d; arg = k; }
-        }
-        lab[p] = valid[p] ? arg : -1;
-        inertia += valid[p] ? best : 0.0;
-        if (valid[p] && labels) labels[id[p]] = arg;
-    }
-    inertia = wave_total_f64(inertia);
-    if (lane == 63) s_part[wave][K * NT] = inertia;
-    for (int k0 = 0; k0 < K; k0 += KM_CHUNK) {
-        double acc[KM_CHUNK][3];
-        unsigned int cnt[KM_CHUNK];
-#pragma unroll
-        for (int j = 0; j < KM_CHUNK; ++j) { acc[j][0] = acc[j][1] = acc[j][2] = 0.0; cnt[j] = 0u; }
-#pragma unroll
-        for (int p = 0; p < KM_PTS; ++p) {
-#pragma unroll
-            for (int j = 0; j < KM_CHUNK; ++j) {
-                const bool mine = lab[p] == k0 + j;
-                cnt[j] += mine ? 1u : 0u;
-                if (SUMS) {
-                    acc[j][0] += mine ? x[p] : 0.0;
-                    acc[j][1] += mine ? y[p] : 0.0;
-                    if (DIM == 3) acc[j][2] += mine ? z[p] : 0.0;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < KM_CHUNK; ++j) {
-            const unsigned int c = wave_incl_scan_add(cnt[j]);   // total in lane 63; every lane takes part
-            if (lane == 63 && k0 + j < K) s_part[wave][(k0 + j) * NT] = __longlong_as_double((long long)c);
-            if (SUMS) {
-#pragma unroll
-                for (int d = 0; d < DIM; ++d) {
-                    const double v = wave_total_f64(acc[j][d]);
-                    if (lane == 63 && k0 + j < K) s_part[wave][(k0 + j) * NT + 1 + d] = v;
-                }
-            }
-        }
-    }
-}
-
-// One Lloyd iteration.  Slab layout: cluster k at [k * (1 + DIM), ...) = N_k (integer), S_k; the inertia at K * (1 + DIM).
-template <int DIM>
-__global__ void __launch_bounds__(KM_BLOCK)
+__global__ void __launch_bounds__(PCR_STREAM_BLOCK)
 kmeans_assign_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_state* __restrict__ st, double* __restrict__ partials,
                      unsigned int* __restrict__ ticket, double* __restrict__ inertia_hist, double* __restrict__ shift_hist) {
-    constexpr int NT = 1 + DIM;
-    __shared__ double s_c[KM_MAX_K * 3];
-    __shared__ double s_part[4][KM_NSUM_MAX], s_red[8][KM_NSUM_MAX], s_tot[KM_NSUM_MAX];
-    if (st->stop) return;
-    km_tile_pass<DIM, true>(pts, n, K, st, nullptr, s_c, s_part);
-    if (!km_block_sums(s_part, K * NT + 1, K, NT, partials, ticket, s_red, s_tot)) return;
-
-    // ---- the last block: the new centres (an empty cluster keeps its own), the shift, the stop rule
-    __shared__ double s_shift[KM_MAX_K];
-    __shared__ int s_empty[KM_MAX_K];
+    __shared__ lloyd_lds<km_cloud_source<DIM>> s;
+    const auto history = [=](int it, double inertia, double shift) {
+        if (inertia_hist) inertia_hist[it] = inertia;
+        if (shift_hist) shift_hist[it] = shift;
+    };
+    if (!lloyd_assign<km_cloud_source<DIM>>(pts, n, DIM, K, st, partials, ticket, s, history)) return;
     const int k = threadIdx.x;
-    if (k < K) {
-        const long long nk = __double_as_longlong(s_tot[k * NT]);
-        double cn[3] = {s_c[3 * k], s_c[3 * k + 1], s_c[3 * k + 2]};
-        if (nk > 0) {
-#pragma unroll
-            for (int d = 0; d < DIM; ++d) cn[d] = s_tot[k * NT + 1 + d] / (double)nk;
-        }
-        const double dx = cn[0] - s_c[3 * k], dy = cn[1] - s_c[3 * k + 1];
-        double q = dx * dx + dy * dy;
-        if (DIM == 3) { const double dz = cn[2] - s_c[3 * k + 2]; q = q + dz * dz; }
-        s_shift[k] = sqrt(q);
-        s_empty[k] = nk > 0 ? 0 : 1;
-        st->counts[k] = nk;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            st->sums[3 * k + d] = d < DIM ? s_tot[k * NT + 1 + d] : 0.0;
-            st->c[3 * k + d] = cn[d];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    double shift = 0.0;
-    int n_empty = 0;
-    for (int j = 0; j < K; ++j) { shift = s_shift[j] > shift ? s_shift[j] : shift; n_empty += s_empty[j]; }
-    const int it = st->it;
-    const double inertia = s_tot[K * NT];
-    if (inertia_hist) inertia_hist[it] = inertia;
-    if (shift_hist) shift_hist[it] = shift;
-    st->inertia = inertia;
-    st->shift = shift;
-    st->n_empty = n_empty;
-    st->it = it + 1;
-    if (shift <= st->tol) { st->converged = 1; st->stop = 1; }
-    else if (it + 1 >= st->max_iter) st->stop = 1;
+    for (int d = 0; d < 3 && k < K; ++d) st->sums[3 * k + d] = d < DIM ? s.tot[k * (1 + DIM) + 1 + d] : 0.0;
 }
 
-// The final pass and predict: labels by CALLER row (the records may be Morton-reordered: id is the row) or none, the counts and the
-// inertia under the centres of `st`.  Slab layout: N_k at [k], the inertia at [K].
 template <int DIM>
-__global__ void __launch_bounds__(KM_BLOCK)
+__global__ void __launch_bounds__(PCR_STREAM_BLOCK)
 kmeans_label_kernel(const pcr_pt* __restrict__ pts, long long n, int K, km_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket,
                     int* __restrict__ labels) {
-    __shared__ double s_c[KM_MAX_K * 3];
-    __shared__ double s_part[4][KM_NSUM_MAX], s_red[8][KM_NSUM_MAX], s_tot[KM_NSUM_MAX];
-    km_tile_pass<DIM, false>(pts, n, K, st, labels, s_c, s_part);
-    if (!km_block_sums(s_part, K + 1, K, 1, partials, ticket, s_red, s_tot)) return;
-    if (threadIdx.x != 0) return;
-    int n_empty = 0;
-    for (int j = 0; j < K; ++j) {
-        const long long nk = __double_as_longlong(s_tot[j]);
-        st->counts[j] = nk;
-        n_empty += nk > 0 ? 0 : 1;
-    }
-    st->n_empty = n_empty;
-    st->inertia = s_tot[K];
+    __shared__ lloyd_lds<km_cloud_source<DIM>> s;
+    lloyd_label<km_cloud_source<DIM>>(pts, n, DIM, K, st, partials, ticket, labels, s);
 }
 
 bool shape_ok(int k, int dim) { return k >= 1 && k <= KM_MAX_K && (dim == 2 || dim == 3); }
@@ -220,7 +82,7 @@ void centers_to_host(const double* c3, int k, int dim, double* out) {
 }
 
 int km_begin(pcr_stream_fit* r, const pcr_cloud* cloud, int k, int dim, const km_state* h) {
-    return pcr_stream_begin(r, cloud, k, dim, KM_TILE, PCR_CW_KMEANS_TICKET, h, sizeof(km_state), KM_NSUM_MAX);
+    return pcr_stream_begin(r, cloud->d, cloud->n, k, dim, KM_TILE, PCR_CW_KMEANS_TICKET, h, sizeof(km_state), KM_NSUM_MAX);
 }
 int km_assign(pcr_stream_fit* r, double* d_inertia_hist, double* d_shift_hist) {
     return pcr_stream_launch(r, kmeans_assign_kernel<2>, kmeans_assign_kernel<3>, d_inertia_hist, d_shift_hist);
@@ -279,7 +141,7 @@ int pcr_kmeans_fit(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_kmeans_params
     PCR_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if ((rc = km_begin(&r, cloud, k, dim, &h[0]))) return rc;
     // one pass per iteration; passes behind a stop return at once.  Then the final pass under the final centres.
-    if ((rc = pcr_stream_loop(&r, max_iter, KM_ITERS_PER_SYNC, KM_HEAD_BYTES, [&](int) { return km_assign(&r, d_inertia_hist, d_shift_hist); }))) return rc;
+    if ((rc = pcr_stream_loop(&r, max_iter, LLOYD_ITERS_PER_SYNC, LLOYD_HEAD_BYTES, [&](int) { return km_assign(&r, d_inertia_hist, d_shift_hist); }))) return rc;
     if ((rc = km_label(&r, d_labels.as<int>()))) return rc;
     PCR_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if ((rc = pcr_d2h_small(ctx, &h[0], r.st.p, sizeof(km_state)))) return rc;

@@ -13,8 +13,7 @@
 //                                 Rayleigh-Ritz step; the p x p result T is left in the loop state
 //               sp_apply_kernel   X <- X T (and Y <- Y T, the residual norms |B u - theta u| and the stop rule)
 //             One read-back of the state's head per outer iteration.
-//   k-means   Lloyd's iteration over the rows of the (n, m) embedding: sp_km_pass_kernel, the slab sums and integer counts of
-//             pcr_kmeans.hip on rows of a matrix; maximin seeds by one block.
+//   k-means   the Lloyd pass of pcr_lloyd.h on the rows of the (n, m) embedding, one row per lane; maximin seeds by one block.
 // No floating-point atomics; every grid depends on n alone: two runs give the same bits.
 #include <algorithm>
 #include <climits>
@@ -22,6 +21,7 @@
 #include <cstring>
 #include <vector>
 #include "pcr_internal.h"
+#include "pcr_lloyd.h"
 #include "pcr_sort.h"
 #include "pcr_spectral_dev.h"
 #include "pcr_stream_fit.h"
@@ -38,8 +38,6 @@ constexpr int SP_DENSE_N = 64;                   // clouds up to this size take 
 constexpr int SP_ROWS = 16;                      // rows per block of the product (256 threads)
 constexpr int SP_APPLY_ROWS = 64;                // rows per block of sp_apply_kernel
 constexpr int SP_GRAM_ROWS = 256;                // rows per block of sp_gram_kernel, staged 64 at a time
-constexpr int SP_KM_NSUM = SP_MAX_K * (1 + SP_MAX_K) + 1;
-constexpr int SP_KM_ITERS_PER_SYNC = 8;
 
 // ---------------------------------------------------------------------------------------------------------------- graph
 struct sp_graph {
@@ -376,6 +374,15 @@ sp_embed_kernel(const double* __restrict__ U, const double* __restrict__ deg, co
     E[rows[i] * m + c] = normalized ? u / sqrt(deg[i]) : u;
 }
 
+// thread 0's pick among the block's 256 candidates (a thread without rows holds row -1): the largest value, the lowest row on ties
+__device__ inline long long sp_pick_row(const double* s_val, const long long* s_row) {
+    double b = -1.0;
+    long long br = -1;
+    for (int t = 0; t < 256; ++t)
+        if (s_row[t] >= 0 && (s_val[t] > b || (s_val[t] == b && s_row[t] < br))) { b = s_val[t]; br = s_row[t]; }
+    return br;
+}
+
 // ONE block: per column the 2-norm (thread t sums the rows t, t + 256, ... in order, thread 0 the 256 partial sums in order) and the
 // entry of largest magnitude, the lowest row on ties -> scale[j] = +-1 / norm
 __global__ void __launch_bounds__(256)
@@ -393,12 +400,9 @@ sp_colscale_kernel(const double* __restrict__ E, long long n, int m, double* __r
         s_sum[threadIdx.x] = sum; s_abs[threadIdx.x] = best; s_row[threadIdx.x] = brow;
         __syncthreads();
         if (threadIdx.x == 0) {
-            double tot = 0.0, b = -1.0;
-            long long br = -1;
-            for (int t = 0; t < 256; ++t) {
-                tot += s_sum[t];
-                if (s_row[t] >= 0 && (s_abs[t] > b || (s_abs[t] == b && s_row[t] < br))) { b = s_abs[t]; br = s_row[t]; }
-            }
+            double tot = 0.0;
+            for (int t = 0; t < 256; ++t) tot += s_sum[t];
+            const long long br = sp_pick_row(s_abs, s_row);
             const double sign = (br >= 0 && E[br * m + j] < 0.0) ? -1.0 : 1.0;
             scale[j] = sign / sqrt(tot);
         }
@@ -413,14 +417,25 @@ sp_scale_kernel(double* __restrict__ E, long long n, int m, const double* __rest
 }
 
 // ---------------------------------------------------------------------------------------------------------------- k-means on rows
-struct __attribute__((aligned(16))) sp_km_state {
-    int it, stop, converged, n_empty;
-    int max_iter, pad;
-    double inertia, shift, tol;
-    double c[SP_MAX_K * SP_MAX_K];       // centres, stride SP_MAX_K
-    long long counts[SP_MAX_K];
+// The rows of an (n, m) matrix, m <= SP_MAX_K at run time: one row per lane, labels by row
+struct sp_row_source {
+    using rec = double;
+    static constexpr int KMAX = SP_MAX_K, CSTRIDE = SP_MAX_K, PTS = 1, DMAX = SP_MAX_K, CHUNK = 1;
+    static constexpr int NSUM = SP_MAX_K * (1 + SP_MAX_K) + 1;
+    __device__ static int dims(int m) { return m; }
+    __device__ static void load(const double* __restrict__ E, long long n, int m, double (&x)[1][DMAX], bool (&valid)[1], long long (&row)[1]) {
+        const long long i = (long long)blockIdx.x * PCR_STREAM_BLOCK + threadIdx.x;
+        valid[0] = i < n;
+        row[0] = i;
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) x[0][d] = (valid[0] && d < m) ? E[i * m + d] : 0.0;
+    }
+};
+
+struct sp_km_state : lloyd_state<SP_MAX_K, SP_MAX_K> {
     long long seeds[SP_MAX_K];
 };
+static_assert(sizeof(sp_km_state) <= PCR_SMALL_D2H_BYTES, "state read back through pcr_d2h_small");
 
 // maximin seeds by ONE block: seed 0 = row 0; seed j = the row with the largest minimum squared distance to the seeds before it
 __global__ void __launch_bounds__(256)
@@ -445,10 +460,7 @@ sp_maximin_kernel(const double* __restrict__ E, long long n, int m, int K, doubl
         s_val[threadIdx.x] = best; s_row[threadIdx.x] = brow;
         __syncthreads();
         if (threadIdx.x == 0) {
-            double b = -1.0;
-            long long br = 0;
-            for (int t = 0; t < 256; ++t)
-                if (s_row[t] >= 0 && (s_val[t] > b || (s_val[t] == b && s_row[t] < br))) { b = s_val[t]; br = s_row[t]; }
+            const long long br = sp_pick_row(s_val, s_row);
             s_last = br;
             st->seeds[j] = br;
         }
@@ -461,86 +473,17 @@ __global__ void sp_km_seed_kernel(const double* __restrict__ E, int m, int K, sp
     if (k < K) st->c[k * SP_MAX_K + d] = d < m ? E[st->seeds[k] * m + d] : 0.0;
 }
 
-// One pass over the rows of E under the centres of the state.  UPDATE: a Lloyd iteration (slab: cluster k at [k (1 + m), ...) = N_k
-// as an integer, S_k; the inertia at K (1 + m)); the last block moves the centres and applies the stop rule.  Else the final pass:
-// labels, counts, inertia.
-template <bool UPDATE>
-__global__ void __launch_bounds__(256)
-sp_km_pass_kernel(const double* __restrict__ E, long long n, int m, int K, sp_km_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket,
-                  int* __restrict__ labels) {
-    __shared__ double s_c[SP_MAX_K * SP_MAX_K];
-    __shared__ double s_part[4][SP_KM_NSUM], s_red[8][SP_KM_NSUM], s_tot[SP_KM_NSUM];
-    if (UPDATE && st->stop) return;
-    const int nt = 1 + m;
-    if (threadIdx.x < SP_MAX_K * SP_MAX_K) s_c[threadIdx.x] = st->c[threadIdx.x];
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n;
-    double x[SP_MAX_K];
-#pragma unroll
-    for (int d = 0; d < SP_MAX_K; ++d) x[d] = (valid && d < m) ? E[i * m + d] : 0.0;
-    __syncthreads();
-    double best = 0.0;
-    int arg = -1;
-    if (valid) {
-        for (int k = 0; k < K; ++k) {
-            const double d0 = x[0] - s_c[k * SP_MAX_K];
-            double d2 = d0 * d0;
-#pragma unroll
-            for (int d = 1; d < SP_MAX_K; ++d)
-                if (d < m) { const double dd = x[d] - s_c[k * SP_MAX_K + d]; d2 = d2 + dd * dd; }
-            if (k == 0 || d2 < best) { best = d2; arg = k; }
-        }
-        if (!UPDATE && labels) labels[i] = arg;
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const double inertia = wave_total_f64(valid ? best : 0.0);
-    if (lane == 63) s_part[wave][K * nt] = inertia;
-    for (int k = 0; k < K; ++k) {
-        const bool mine = arg == k;
-        const unsigned int cnt = wave_incl_scan_add(mine ? 1u : 0u);
-        if (lane == 63) s_part[wave][k * nt] = __longlong_as_double((long long)cnt);
-#pragma unroll
-        for (int d = 0; d < SP_MAX_K; ++d) {
-            if (d < m) {   // (uniform)
-                const double v = wave_total_f64(mine ? x[d] : 0.0);
-                if (lane == 63) s_part[wave][k * nt + 1 + d] = v;
-            }
-        }
-    }
-    if (!block_slab_sums<SP_KM_NSUM>(s_part, K * nt + 1, partials, ticket, s_red, s_tot, [K, nt](double a, double b, int t) {
-            const bool count = t < K * nt && t % nt == 0;
-            return count ? __longlong_as_double(__double_as_longlong(a) + __double_as_longlong(b)) : a + b;
-        }))
-        return;
-    if (threadIdx.x != 0) return;
-    int n_empty = 0;
-    double shift = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const long long nk = __double_as_longlong(s_tot[k * nt]);
-        st->counts[k] = nk;
-        n_empty += nk > 0 ? 0 : 1;
-        if (UPDATE) {
-            double q = 0.0;
-            for (int d = 0; d < m; ++d) {
-                const double old = s_c[k * SP_MAX_K + d];
-                const double cn = nk > 0 ? s_tot[k * nt + 1 + d] / (double)nk : old;
-                const double dd = cn - old;
-                q = d == 0 ? dd * dd : q + dd * dd;
-                st->c[k * SP_MAX_K + d] = cn;
-            }
-            const double s = sqrt(q);
-            shift = s > shift ? s : shift;
-        }
-    }
-    st->n_empty = n_empty;
-    st->inertia = s_tot[K * nt];
-    if (UPDATE) {
-        const int it = st->it;
-        st->shift = shift;
-        st->it = it + 1;
-        if (shift <= st->tol) { st->converged = 1; st->stop = 1; }
-        else if (it + 1 >= st->max_iter) st->stop = 1;
-    }
+__global__ void __launch_bounds__(PCR_STREAM_BLOCK)
+sp_km_assign_kernel(const double* __restrict__ E, long long n, int K, sp_km_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket, int m) {
+    __shared__ lloyd_lds<sp_row_source> s;
+    lloyd_assign<sp_row_source>(E, n, m, K, st, partials, ticket, s, [](int, double, double) {});
+}
+
+__global__ void __launch_bounds__(PCR_STREAM_BLOCK)
+sp_km_label_kernel(const double* __restrict__ E, long long n, int K, sp_km_state* __restrict__ st, double* __restrict__ partials, unsigned int* __restrict__ ticket, int m,
+                   int* __restrict__ labels) {
+    __shared__ lloyd_lds<sp_row_source> s;
+    lloyd_label<sp_row_source>(E, n, m, K, st, partials, ticket, labels, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -735,32 +678,22 @@ int spectral_run(pcr_ctx* ctx, const pcr_cloud* cloud, const pcr_spectral_params
 
     // ---- K-Means on the rows of the embedding
     PCR_HIP(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    pcr_dev_block d_st(ctx), d_mind(ctx), d_labels(ctx);
-    if ((rc = d_st.alloc(sizeof(sp_km_state))) || (rc = d_mind.alloc(8 * n)) || (rc = d_labels.alloc(4 * n))) return rc;
-    const unsigned g_km = (unsigned)((n + 255) / 256);
-    if ((rc = pcr_ensure_scratch(ctx, sizeof(double) * (size_t)g_km * SP_KM_NSUM))) return rc;
-    unsigned int* ticket = pcr_counter(ctx, PCR_CW_SPECTRAL_TICKET);
+    pcr_stream_fit r(ctx);
+    pcr_dev_block d_mind(ctx), d_labels(ctx);
+    if ((rc = d_mind.alloc(8 * n)) || (rc = d_labels.alloc(4 * n))) return rc;
     std::vector<sp_km_state> h(1);
     memset(&h[0], 0, sizeof(sp_km_state));
     h[0].max_iter = params->kmeans_max_iter;
     h[0].tol = params->kmeans_tol;
     if (seed_rows) for (int j = 0; j < K; ++j) h[0].seeds[j] = seed_rows[j];
-    sp_km_state* st = d_st.as<sp_km_state>();
-    PCR_HIP(ctx, hipMemcpyAsync(st, &h[0], sizeof(sp_km_state), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pcr_stream_begin(&r, d_E.p, n, K, m, PCR_STREAM_BLOCK, PCR_CW_SPECTRAL_TICKET, &h[0], sizeof(sp_km_state), sp_row_source::NSUM))) return rc;
+    sp_km_state* st = r.st.as<sp_km_state>();
     if (!seed_rows) hipLaunchKernelGGL(sp_maximin_kernel, dim3(1), dim3(256), 0, ctx->stream, d_E.as<const double>(), n, m, K, d_mind.as<double>(), st);
     hipLaunchKernelGGL(sp_km_seed_kernel, dim3(1), dim3(SP_MAX_K * SP_MAX_K), 0, ctx->stream, d_E.as<const double>(), m, K, st);
     PCR_HIP(ctx, hipGetLastError());
-    for (int i = 0; i < params->kmeans_max_iter; ++i) {
-        hipLaunchKernelGGL(sp_km_pass_kernel<true>, dim3(g_km), dim3(256), 0, ctx->stream, d_E.as<const double>(), n, m, K, st, ctx->d_partials, ticket, (int*)nullptr);
-        PCR_HIP(ctx, hipGetLastError());
-        if (i + 1 == params->kmeans_max_iter || (i + 1) % SP_KM_ITERS_PER_SYNC == 0) {
-            pcr_stream_head head;
-            if ((rc = pcr_d2h_small(ctx, &head, st, sizeof(head)))) return rc;
-            if (head.stop) break;
-        }
-    }
-    hipLaunchKernelGGL(sp_km_pass_kernel<false>, dim3(g_km), dim3(256), 0, ctx->stream, d_E.as<const double>(), n, m, K, st, ctx->d_partials, ticket, d_labels.as<int>());
-    PCR_HIP(ctx, hipGetLastError());
+    if ((rc = pcr_stream_loop(&r, params->kmeans_max_iter, LLOYD_ITERS_PER_SYNC, LLOYD_HEAD_BYTES, [&](int) { return pcr_stream_launch_one(&r, sp_km_assign_kernel, m); })))
+        return rc;
+    if ((rc = pcr_stream_launch_one(&r, sp_km_label_kernel, m, d_labels.as<int>()))) return rc;
     PCR_HIP(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     if ((rc = pcr_d2h_small(ctx, &h[0], st, sizeof(sp_km_state)))) return rc;
     res->kmeans_iters = h[0].it;

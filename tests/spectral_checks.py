@@ -28,6 +28,14 @@ def bridge(n, seed=0):
     return pts
 
 
+def chain(n, seed=0):
+    """Eight elongated blobs 4.5 apart in a row, each touching the next: one component.  The first n % 8 blobs hold one point more."""
+    rng = np.random.default_rng(seed)
+    pts = np.vstack([rng.normal(size=(n // 8 + (1 if i < n % 8 else 0), 3)) * [1, 1.7, .4] + [4.5 * i, 0, 0] for i in range(8)])
+    pts.setflags(write=False)
+    return pts
+
+
 def blobs_even(n, seed=0):
     """Three blobs of n // 3 points each at the lidar centres of ``lidar``: three components of equal size."""
     rng = np.random.default_rng(seed)

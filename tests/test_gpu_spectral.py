@@ -147,6 +147,28 @@ def test_labels_against_the_restated_lloyd(pcp, ctx, n):
     assert np.array_equal(model.labels_[sure], km["labels"][sure])
 
 
+@pytest.mark.parametrize("n", [521, 2049])
+def test_kmeans_stage_at_eight_clusters(pcp, ctx, n):
+    """k = 8 fills every slab slot and every centre row of the K-Means stage.  The restatement runs on the device's own embedding
+    from the device's seeds, so the eigensolver's freedom is no part of the comparison; no row is left out."""
+    model = pcp.spetral_clustering(8).fit(data_of("chain", n), ctx=ctx)
+    E = model.embedding_
+    print("solver converged", model.converged_, "iterations", model.n_iter_)
+    assert E.shape == (n, 8) and len(set(model.seed_rows_)) == 8
+    km = sc.kmeans_checks.fit(E, E[model.seed_rows_], max_iter=300, tol=1e-4)
+    print("iterations", km["n_iter"], "smallest assignment gap", km["min_gap"].min())
+    assert km["min_gap"].min() > 1e-9          # nothing that rounding could decide
+    assert model.kmeans_iter_ == km["n_iter"] and model.kmeans_converged_
+    assert np.array_equal(model.labels_, km["labels"])
+    assert np.array_equal(np.bincount(model.labels_, minlength=8), km["counts"])
+    # sums of n entries of unit-norm columns (|E| <= 1) in another order, then the division
+    err = np.abs(model.centers_ - km["centers"]).max()
+    rel = abs(model.inertia_ - km["inertia"]) / km["inertia"]
+    print("centres: largest difference", err, "bound", 2 * n * 2.0 ** -53, "inertia: relative difference", rel, "bound", n * 2.0 ** -52)
+    assert err <= 2 * n * 2.0 ** -53
+    assert rel <= n * 2.0 ** -52
+
+
 @pytest.mark.parametrize("name", ["bridge", "blobs_norm", "blobs_raw"])
 def test_golden_partitions(pcp, ctx, name):
     g = load_golden("spectral.npz")
