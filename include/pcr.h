@@ -151,7 +151,7 @@ typedef struct pcr_icp_result {
     double mean_d2;        /* mean squared NN distance of the last association pass     */
     double r_diff[PCR_ICP_MAX_LOG]; /* log["R_diff"], icp_template.py:189 */
     double t_diff[PCR_ICP_MAX_LOG]; /* log["t_diff"], icp_template.py:190 */
-    double device_ms;      /* duration of the whole loop on the device: the kernels' own 100-MHz clock, first kernel .. end of the last pass (device-resident loop), HIP events otherwise */
+    double device_ms;      /* duration of the whole loop on the device: the kernels' own 100-MHz clock, first kernel .. the last pass's state written (device-resident loop; in a one-launch pass the wave that writes it is the last to add to the sums, not the last to leave: the kernel itself ends a microsecond or two later), HIP events otherwise */
     double nn_kernel_ms;   /* sum of HIP-event times of the pass kernels; 0 unless pcr_profile_enable(ctx, 1) (host loop: always) */
     int32_t nn_launches;   /* launches of the correspondence kernel                     */
     int32_t reserved;      /* diagnostic: 1 when the fused stages of pcr_icp_batch / pcr_register_pairs produced this result, 0 from pcr_icp (and from the batch's per-pair path) */

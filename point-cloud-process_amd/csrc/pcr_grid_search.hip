@@ -1004,7 +1004,7 @@ grid_hard_kernel(pcr_grid_view gv, const work_item* __restrict__ list, const uns
 // ------------------------------------------------------------------------------------------------ one-kernel ICP pass
 // One launch per ICP iteration of the device-resident loop: every wave runs its tile, adds the moments of the queries it
 // proved, hands what it could not prove to a work queue, then serves that queue (one query per wave, hard_search) until
-// its group of tiles has nothing left; the wave that leaves last solves the Procrustes step.  Against tile kernel ->
+// its group of tiles has nothing left; the wave whose contribution lands last solves the Procrustes step.  Against tile kernel ->
 // hard kernel this removes a launch boundary and, more important, the hard items start while slow tiles are still
 // running (the tile stage is one generation of waves: its tail left most of the chip idle).
 //
@@ -1042,12 +1042,15 @@ grid_hard_kernel(pcr_grid_view gv, const work_item* __restrict__ list, const uns
 //             and leaves otherwise.  Progress: the last generation of waves waits, and serves what the earlier ones left.
 //   variants  inline_queue = 0: the launch only publishes and grid_drain_kernel (below) serves the queues -- the host's choice
 //             while several ICP loops of the process are in flight; same results bit for bit.
-//   finish    vmcnt(0) (own atomics acknowledged), then a two-level ticket (one word per group, then a root).
+//   finish    one launch: landed counts (below) -- the wave whose moments are acknowledged last runs the step while the waiters
+//             read the poison and leave; every wave: vmcnt(0) (own atomics acknowledged), then a two-level ticket (one word per
+//             group, then a root).  The wave that takes the last ticket cleans the queue words and, if the pass had no finisher,
+//             serves what is left and runs the step.
 constexpr int ACC_SETS = 32;
 constexpr double GATE_KAPPA = 1.25;                       // search radius, in gate radii, of a queue item without a candidate (carried gate bounds)
 constexpr int PASS_GROUPS = 32;
-constexpr int PASS_SYNC_STRIDE = 32;                      // 64-bit words per group: queue word at 0, started at 16, ticket at 17 (other line)
-constexpr int PASS_SYNC_WORDS = PASS_SYNC_STRIDE * (PASS_GROUPS + 1);   // + root ticket (0) / error word (16)
+constexpr int PASS_SYNC_STRIDE = 32;                      // 64-bit words per group: queue word at 0, started at 16, ticket at 17, landed at 18 (other line)
+constexpr int PASS_SYNC_WORDS = PASS_SYNC_STRIDE * (PASS_GROUPS + 1);   // + root ticket (0) / poison count (8) / error word (16) / groups landed (24)
 constexpr unsigned long long ITEM_NONE = ~0ull;           // "not written yet": never a valid word of an item
 // Last word of an item = query index | binary32 bits of its candidate's bound << 32 (finite, or +inf).  A POISON word carries 0xfffffffe
 // (no such bound) above the id of the pass that wrote it: poison of an earlier pass reads as "not written yet", so nobody ever has to
@@ -1120,6 +1123,54 @@ __device__ static inline void st_dev(unsigned long long* p, unsigned long long v
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- Landed counts of the one-launch pass: who runs the Procrustes step.  One more word per group, in the line of its started
+// count and ticket (both quiet while tiles end; the queue word's line takes every reservation and claim):
+//     items landed << 42 | items published << 20 | tiles landed
+// counted over the group's TILES and the items THEY published, wherever those were served ((qi / WT_Q) % PASS_GROUPS is the
+// publisher's group).  A contribution is reported -- one returning add -- once its accumulator atomics are acknowledged
+// (s_waitcnt vmcnt(0): atomics without return count there).  A tile's add carries its own item count, so "published" is final with
+// the group's last tile; items may land before that, hence separate fields and equality as the only test: exactly one add per
+// pass leaves a group at `tiles == g_tiles && landed == published`, that add bumps the root count, and the add that completes the
+// last group makes its wave the pass's finisher (returns true for it).
+constexpr int LAND_WORD = 18, LAND_ROOT = 24;             // word of a group's slice / of the root slice (groups complete)
+constexpr int LAND_PUB_SHIFT = 20, LAND_IN_SHIFT = 42;
+constexpr unsigned long long LAND_TILE_MASK = (1ull << LAND_PUB_SHIFT) - 1ull;
+constexpr unsigned long long TICKET_FIN = 1ull << 63;     // in a group or root ticket: the step of this pass has been run by the last lander
+static_assert(LAND_IN_SHIFT - LAND_PUB_SHIFT == Q_BITS && LAND_IN_SHIFT + Q_BITS == 64, "landed word: 20 + 22 + 22 bits");
+// lane 0: `now` = a group's landed word after this wave's add: is the group complete?
+__device__ __forceinline__ static bool land_complete(unsigned long long now, unsigned int g_tiles) {
+    return (unsigned int)(now & LAND_TILE_MASK) == g_tiles && ((now >> LAND_PUB_SHIFT) & Q_MASK) == (now >> LAND_IN_SHIFT);
+}
+// an item server's report, behind pass_serve_item (the whole wave calls; the answer is wave-uniform)
+__device__ __forceinline__ static bool land_report_item(unsigned long long* sync, int lane, unsigned int qi, unsigned int n_waves, unsigned int n_groups) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the item's moments are acknowledged
+    int fin = 0;
+    if (lane == 0) {
+        const unsigned int pg = (qi / WT_Q) % PASS_GROUPS;
+        const unsigned long long now = __hip_atomic_fetch_add(sync + (size_t)PASS_SYNC_STRIDE * pg + LAND_WORD, 1ull << LAND_IN_SHIFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
+                                       (1ull << LAND_IN_SHIFT);
+        if (land_complete(now, n_waves / PASS_GROUPS + (pg < n_waves % PASS_GROUPS ? 1u : 0u)))
+            fin = __hip_atomic_fetch_add(sync + (size_t)PASS_SYNC_STRIDE * PASS_GROUPS + LAND_ROOT, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)(n_groups - 1u) ? 1 : 0;
+    }
+    return __builtin_amdgcn_readfirstlane(fin) != 0;
+}
+// Second level of the ticket (lane 0, the wave that took the last ticket of its group): 0 = not the launch's last wave; else 1 =
+// every group reported a wave that left by the poison, 2 = look for unclaimed items, 3 = somebody gave up: look at every reserved
+// slot.  fin_seen: the pass has a finisher (this wave, or one whose mark travelled up through the tickets).
+__device__ __forceinline__ static int ticket_root(unsigned long long* root, unsigned long long tg_old, bool left_by_poison, bool failed, bool fin, unsigned int n_groups,
+                                                  int& fin_seen) {
+    const bool g_clean = ((tg_old >> 32) & 0xffffull) != 0 || left_by_poison;
+    const bool g_failed = ((tg_old >> 48) & 0x7fffull) != 0 || failed;
+    const bool g_fin = (tg_old & TICKET_FIN) != 0 || fin;
+    const unsigned long long tr_old = __hip_atomic_fetch_add(root, 1ull | (g_clean ? 1ull << 32 : 0ull) | (g_failed ? 1ull << 48 : 0ull) | (g_fin ? TICKET_FIN : 0ull), __ATOMIC_RELAXED,
+                                                             __HIP_MEMORY_SCOPE_AGENT);
+    if ((unsigned int)tr_old != n_groups - 1u) return 0;
+    fin_seen = ((tr_old & TICKET_FIN) != 0 || g_fin) ? 1 : 0;
+    int last = ((unsigned int)((tr_old >> 32) & 0xffffull) + (g_clean ? 1u : 0u) == n_groups) ? 1 : 2;
+    if (((tr_old >> 48) & 0x7fffull) != 0 || g_failed) last = 3;
+    return last;
+}
+
 union pass_lds {
     wtile_lds t;
     hard_lds h;
@@ -1127,8 +1178,9 @@ union pass_lds {
     long long xll[WT_Q * (PCR_NMOM - 1)];
 };
 
-// one queued query, served by the calling wave: exact search, then its moments (rounded to fixed point once) and its result
-__device__ __forceinline__ static void pass_serve_item(const pcr_grid_view& gv, pass_lds* L, const int lane, const unsigned long long w, const double max_d2,
+// one queued query, served by the calling wave: exact search, then its moments (rounded to fixed point once) and its result;
+// returns the query's index (wave-uniform)
+__device__ __forceinline__ static unsigned int pass_serve_item(const pcr_grid_view& gv, pass_lds* L, const int lane, const unsigned long long w, const double max_d2,
                                                        const pass_args& A, unsigned int* __restrict__ res_pos, unsigned long long* __restrict__ dbg,
                                                        const unsigned int dbg_slot, const unsigned long long t_start) {
     // lanes 0..3 hold the item's four words
@@ -1186,13 +1238,20 @@ __device__ __forceinline__ static void pass_serve_item(const pcr_grid_view& gv, 
             dbg[(1 << 17) + dbg_slot * 4 + 3] = (unsigned long long)have_cand | ((unsigned long long)(s_level0 + 1) << 8);
         }
     }
+    return qi;
 }
 
-// The wave that leaves a pass last: totals of the fixed-point accumulators -> Procrustes step -> convergence test -> loop state.
+// The wave that finishes a pass: totals of the fixed-point accumulators -> Procrustes step -> convergence test -> loop state.
 // lane l < 60 owns moment l % 20 of every third set: independent loads, integer sums (order irrelevant), words zeroed behind.
 // The head of the loop state travels with them (one 8-byte word per lane) into LDS: the step reads and updates ~50 of its words.
+// after_sums() runs when the totals are in registers, in front of the step: the one-launch pass's last lander takes its ticket there
+// (the reply returns underneath the step, and the loads of the totals do not queue behind a ticket word the leaving waiters add to).
+struct finish_nothing {
+    __device__ void operator()() const {}
+};
+template <class AFTER = finish_nothing>
 __device__ __forceinline__ static void pass_finish(const pcr_grid_view& gv, pass_lds* L, const int lane, const pass_args& A, unsigned long long* root,
-                                                   unsigned long long* __restrict__ dbg) {
+                                                   unsigned long long* __restrict__ dbg, AFTER after_sums = AFTER()) {
     constexpr int HEAD_WORDS = (int)(pcr::ICP_STATE_HEAD_BYTES / 8);
     static_assert(pcr::ICP_STATE_HEAD_BYTES % 8 == 0 && HEAD_WORDS <= 64, "state head: one word per lane");
     double* const head = L->xch + 32;   // 16-byte aligned, behind the 20 moments
@@ -1201,14 +1260,14 @@ __device__ __forceinline__ static void pass_finish(const pcr_grid_view& gv, pass
     if (lane == 63) err_w = ld_dev(root + 16);   // (with the other loads: one round trip)
     const int mom = lane % PCR_NMOM, part = lane / PCR_NMOM;
     long long sum = 0;
-    if (part < 3) {
-        constexpr int PER = (ACC_SETS + 2) / 3;
-        unsigned long long v[PER];
+    constexpr int PER = (ACC_SETS + 2) / 3;
+    unsigned long long v[PER];
 #pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int set = part + 3 * j;
-            v[j] = set < ACC_SETS ? ld_dev(A.acc + (size_t)set * PCR_NMOM + mom) : 0ull;
-        }
+    for (int j = 0; j < PER; ++j) {
+        const int set = part + 3 * j;
+        v[j] = (part < 3 && set < ACC_SETS) ? ld_dev(A.acc + (size_t)set * PCR_NMOM + mom) : 0ull;
+    }
+    if (part < 3) {
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const int set = part + 3 * j;
@@ -1216,6 +1275,7 @@ __device__ __forceinline__ static void pass_finish(const pcr_grid_view& gv, pass
             sum += (long long)v[j];
         }
     }
+    after_sums();
     if (dbg && lane == 0) dbg[(1 << 19) - 4] = __builtin_amdgcn_s_memrealtime();
     sum += __shfl(sum, lane + PCR_NMOM, 64) + __shfl(sum, lane + 2 * PCR_NMOM, 64);   // lanes 0..19: all three parts
     wave_sync();
@@ -1463,6 +1523,8 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
     tile_fold_moments(L, lane, S, P, nb, gv.origin, max_d2, A.prev_xyz, A.scale, A.lin, A.acc, tile);
     wave_sync();
     // ---- the reply of the done-add: this wave's first slot, and whether it was the last tile of its group
+    int fin = 0;   // (wave-uniform) 1 / 2: this wave -- as a tile / as an item server -- is the pass's last lander and runs the step
+    unsigned long long rt_fin = 0;
     {
         {
             const unsigned int o_lo = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)own), o_hi = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(own >> 32));
@@ -1472,23 +1534,39 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
             have_claim = true;
             mine = (unsigned int)((own >> Q_BITS) & Q_MASK);
         }
-        if ((unsigned int)(own >> (2 * Q_BITS)) == g_tiles - 1u && inline_queue) {
-            // last tile of its group.  The last GROUP to get there knows that every reservation of the launch is in place: it
-            // poisons the slots [R, R + waves of the group) of every group -- whoever waits there holds an index that will never
-            // be filled (each wave exactly one), reads that and leaves.
-            int fin = 0;
-            if (lane == 0) fin = __hip_atomic_fetch_add(root + 8, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned long long)(n_groups - 1u) ? 1 : 0;
-            if (__builtin_amdgcn_readfirstlane(fin)) {
-                if (lane == 0) st_dev(root + 8, 0ull);
-                unsigned long long qw = 0;
-                if (lane < (int)n_groups) qw = ld_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane);
-                const unsigned int R_l = (unsigned int)(qw & Q_MASK);
-                for (unsigned int gg = 0; gg < n_groups; ++gg) {
-                    const unsigned int R = (unsigned int)__builtin_amdgcn_readlane((int)R_l, (int)gg);
-                    const unsigned int gt = n_waves / PASS_GROUPS + (gg < n_waves % PASS_GROUPS ? 1u : 0u);
-                    unsigned long long* const base_g = A.items + (size_t)gg * A.cap * 4;
-                    for (unsigned int k = lane; k < gt; k += 64) st_dev(base_g + (size_t)(R + k) * 4 + 3, item_poison(A.pass_id));
-                }
+        const bool g_last_tile = (unsigned int)(own >> (2 * Q_BITS)) == g_tiles - 1u && inline_queue;
+        // Two chains leave from here, and they share their round trips: each pair of accesses below is in flight together.
+        //   landed   the tile's contribution has landed when its moment atomics are acknowledged: lane 0 reports it with the items
+        //            the tile published (landed counts, above); the add that completes the group bumps the root count, and the
+        //            one that completes the last group makes this wave the finisher;
+        //   poison   the last tile of its group (lane 1) bumps the poison count.  The last GROUP to get there knows that every
+        //            reservation of the launch is in place: it poisons the slots [R, R + waves of the group) of every group --
+        //            whoever waits there holds an index that will never be filled (each wave exactly one), reads that and leaves.
+        unsigned long long rep = 0;   // lane 0: the group's landed word behind this add; lane 1: the poison count behind this add
+        if (inline_queue) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const unsigned long long inc = lane == 0 ? (1ull | ((unsigned long long)__popcll(um) << LAND_PUB_SHIFT)) : 1ull;
+            unsigned long long* const p = lane == 0 ? g_q + LAND_WORD : root + 8;
+            if (lane == 0 || (lane == 1 && g_last_tile)) rep = __hip_atomic_fetch_add(p, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + inc;
+        }
+        const unsigned long long land_now = ((unsigned long long)(unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(rep >> 32), 0) << 32) | (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)rep, 0);
+        const bool g_landed = inline_queue && land_complete(land_now, g_tiles);
+        const bool psn = g_last_tile && (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)rep, 1) == n_groups;
+        unsigned long long c_old = 0, qw = 0;
+        if (g_landed && lane == 0) c_old = __hip_atomic_fetch_add(root + LAND_ROOT, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (psn) {
+            if (lane == 0) st_dev(root + 8, 0ull);
+            if (lane < (int)n_groups) qw = ld_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane);
+        }
+        if (g_landed) fin = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)c_old) == n_groups - 1u ? 1 : 0;
+        if (dbg && fin) rt_fin = __builtin_amdgcn_s_memrealtime();
+        if (psn) {
+            const unsigned int R_l = (unsigned int)(qw & Q_MASK);
+            for (unsigned int gg = 0; gg < n_groups; ++gg) {
+                const unsigned int R = (unsigned int)__builtin_amdgcn_readlane((int)R_l, (int)gg);
+                const unsigned int gt = n_waves / PASS_GROUPS + (gg < n_waves % PASS_GROUPS ? 1u : 0u);
+                unsigned long long* const base_g = A.items + (size_t)gg * A.cap * 4;
+                for (unsigned int k = lane; k < gt; k += 64) st_dev(base_g + (size_t)(R + k) * 4 + 3, item_poison(A.pass_id));
             }
         }
     }
@@ -1501,8 +1579,10 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
     }
     if (!inline_queue) return;   // throughput variant: grid_drain_kernel serves the queues and finishes
     // ---- serve the group's queue
+    // (the finisher skips, or leaves, the loop: every item of the launch has landed, so the slot it holds lies at or behind the final
+    // count of its group -- nothing will ever arrive there but the poison)
     bool failed = false, left_by_poison = false;
-    for (;;) {
+    while (!fin) {
         if (!have_claim) {
             if (!all_started) {
                 unsigned long long sv = 0;
@@ -1552,43 +1632,55 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
         if (poisoned) { left_by_poison = true; break; }
         if (lane < 4) st_dev(it + lane, ITEM_NONE);   // the slot is clean for the next launch
         ++n_items;
-        pass_serve_item(gv, L, lane, w, max_d2, A, res_pos, dbg, g + PASS_GROUPS * mine, t_start);
-    }
-    const unsigned long long rt_loop = dbg ? __builtin_amdgcn_s_memrealtime() : 0;
-    // ---- the wave that leaves last converts the totals, solves the Procrustes step and tests convergence
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int last = 0;
-    {
-        // Tickets carry a second count in their upper half: waves that left the queue by reading the poison.  Such a wave held an
-        // index >= the final slot count of its group, so every slot below it had been claimed: a group with one of them has nothing
-        // unclaimed, and when every group has one the last wave need not look at the queue words at all.
-        // (third field, bits 48+: waves that gave up waiting -- each holds a slot index whose item came, or will have come, after it left)
-        if (lane == 0) {
-            const unsigned long long tg_old = __hip_atomic_fetch_add(g_ticket, 1ull | (left_by_poison ? 1ull << 32 : 0ull) | (failed ? 1ull << 48 : 0ull), __ATOMIC_RELAXED,
-                                                                     __HIP_MEMORY_SCOPE_AGENT);
-            if ((unsigned int)tg_old == g_tiles - 1u) {
-                const bool g_clean = ((tg_old >> 32) & 0xffffull) != 0 || left_by_poison;
-                const bool g_failed = (tg_old >> 48) != 0 || failed;
-                const unsigned long long tr_old = __hip_atomic_fetch_add(root, 1ull | (g_clean ? 1ull << 32 : 0ull) | (g_failed ? 1ull << 48 : 0ull), __ATOMIC_RELAXED,
-                                                                         __HIP_MEMORY_SCOPE_AGENT);
-                if ((unsigned int)tr_old == n_groups - 1u) {
-                    last = ((unsigned int)((tr_old >> 32) & 0xffffull) + (g_clean ? 1u : 0u) == n_groups) ? 1 : 2;   // 2: look for unclaimed items
-                    if ((tr_old >> 48) != 0 || g_failed) last = 3;                                                    // 3: somebody gave up: look at every reserved slot
-                }
-            }
+        const unsigned int qi_served = pass_serve_item(gv, L, lane, w, max_d2, A, res_pos, dbg, g + PASS_GROUPS * mine, t_start);
+        if (land_report_item(A.sync, lane, qi_served, n_waves, n_groups)) {
+            fin = 2;
+            if (dbg) rt_fin = __builtin_amdgcn_s_memrealtime();
         }
     }
-    if (dbg && lane == 0) {
-        unsigned long long* d = dbg + (1 << 19) + (size_t)(blockIdx.x * 4 + wave) * 8;
-        d[0] = rt_start; d[1] = rt_tile; d[2] = rt_acc; d[3] = rt_loop; d[4] = n_items; d[5] = n_polls | ((unsigned long long)n_casfail << 32); d[6] = S.dbg_pairs | ((unsigned long long)S.dbg_passes << 40) | ((unsigned long long)__popcll(um) << 48); d[7] = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long rt_loop = dbg ? __builtin_amdgcn_s_memrealtime() : 0;
+    // ---- The Procrustes step -- totals, solve, convergence test -- is run by the wave whose contribution landed last (fin).  Beside
+    // it the waiters read the poison and everybody takes a ticket; the wave that LEAVES last cleans the queue words, and it is the
+    // fall-back: where no finisher arose (nobody was obliged to wait and an item stayed unclaimed, or a waiter gave up on a slot
+    // whose item came later) it serves what is left and runs the step itself, as every pass used to end.  The finisher marks its
+    // ticket, the mark travels up like the other fields, and a last leaver that sees it never runs the step a second time.
+    int last = 0, fin_seen = 0;
+    // Tickets carry a second count in their upper half: waves that left the queue by reading the poison.  Such a wave held an
+    // index >= the final slot count of its group, so every slot below it had been claimed: a group with one of them has nothing
+    // unclaimed, and when every group has one the last wave need not look at the queue words at all.
+    // (third field, bits 48..62: waves that gave up waiting -- each holds a slot index whose item came, or will have come, after it
+    // left; bit 63: the finisher's mark)
+    // The finisher has nothing more to say to the queue and all it added is acknowledged (its report waited for that): it does not
+    // wait here, and pass_finish issues its ticket once the totals are in registers -- the reply comes back underneath the step,
+    // and the loads do not queue behind a ticket word that the leaving waiters are hammering.  (A finisher that also wrote the
+    // poison -- the last tile, when no item lands behind it: one pass in five on the 120 k pair -- still waits for those 3 752
+    // scattered stores with its loads, 7 us instead of 2.5: the memory counter is in order.  Writing them behind the loads, or behind
+    // the sums, measured the same: issuing them alone takes the wave 4 us)
+    unsigned long long tg_old = 0;
+    if (!fin) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (lane == 0)
+            tg_old = __hip_atomic_fetch_add(g_ticket, 1ull | (left_by_poison ? 1ull << 32 : 0ull) | (failed ? 1ull << 48 : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    last = __builtin_amdgcn_readfirstlane(last);
-    if (!last) return;
+    auto stamp_wave = [&]() {
+        if (dbg && lane == 0) {
+            unsigned long long* d = dbg + (1 << 19) + (size_t)(blockIdx.x * 4 + wave) * 8;
+            d[0] = rt_start; d[1] = rt_tile; d[2] = rt_acc; d[3] = rt_loop; d[4] = n_items; d[5] = n_polls | ((unsigned long long)n_casfail << 32); d[6] = S.dbg_pairs | ((unsigned long long)S.dbg_passes << 40) | ((unsigned long long)__popcll(um) << 48); d[7] = __builtin_amdgcn_s_memrealtime();
+        }
+    };
+    if (!fin) {
+        if (lane == 0 && (unsigned int)tg_old == g_tiles - 1u) last = ticket_root(root, tg_old, left_by_poison, failed, false, n_groups, fin_seen);
+        stamp_wave();
+        last = __builtin_amdgcn_readfirstlane(last);
+        if (!last) return;
+        fin_seen = __builtin_amdgcn_readfirstlane(fin_seen);
+    }
     // ---- last wave of the launch.  Nobody is OBLIGED to wait for work (a wave that cannot see every tile of the launch started
     // leaves when it finds nothing), so items reserved after the last wave of their group left may still sit in the queue: unless
     // every group reported a wave that left by the poison, look for them and serve them here.  Then clean the queue words.
+    // (With a finisher there is nothing left: every item published has landed.)
     if (last == 3 && dbg_arg && lane == 0) atomicAdd(&dbg_arg[(1 << 19) - 16], 1ull);   // (PCR_DEBUG_STAMPS: passes in which a waiter gave up)
-    if (last >= 2) {
+    if (last >= 2 && !fin_seen) {
         unsigned long long qw = 0;
         if (lane < (int)n_groups) qw = ld_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane);
         const unsigned int r_l = (unsigned int)(qw & Q_MASK);
@@ -1624,13 +1716,44 @@ grid_pass_kernel(const pcr_grid_view* __restrict__ gvp, pcr_grid_view gv, pcr_pt
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the leftovers' atomics
     }
-    if (lane < (int)n_groups) {   // (stores: nobody waits for them)
-        st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane, 0ull);
-        st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + 16, 0ull);
-        st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + 17, 0ull);
+    auto clean_sync = [&]() {   // by the wave that leaves last (stores: nobody waits for them)
+        if (lane < (int)n_groups) {
+            st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane, 0ull);
+            st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + 16, 0ull);
+            st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + 17, 0ull);
+        }
+        if (lane == 0) st_dev(root, 0ull);
+    };
+    if (!fin) {
+        clean_sync();
+        if (fin_seen) return;   // the step has been run
+        // no finisher: some group never completed (the leftovers above were not reported), and every wave has made its reports
+        if (lane < (int)n_groups) st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + LAND_WORD, 0ull);
+        if (lane == 0) st_dev(root + LAND_ROOT, 0ull);
     }
-    if (lane == 0) st_dev(root, 0ull);
-    pass_finish(gv, L, lane, A, root, dbg);
+    // (PCR_DEBUG_STAMPS: passes finished by the last lander / by the last leaver, next to the give-ups: together every pass that ran)
+    if (dbg_arg && lane == 0) atomicAdd(&dbg_arg[(1 << 19) - (fin ? 15 : 14)], 1ull);
+    if (dbg && lane == 0) {
+        dbg[(1 << 19) - 6] = fin ? (unsigned long long)fin : 3ull;
+        dbg[(1 << 19) - 5] = fin ? rt_fin : __builtin_amdgcn_s_memrealtime();
+    }
+    if (fin) __builtin_amdgcn_s_setprio(3);   // (the step is one lane's serial work, beside waves that poll and leave)
+    pass_finish(gv, L, lane, A, root, dbg, [&]() {
+        if (!fin) return;
+        if (lane == 0) tg_old = __hip_atomic_fetch_add(g_ticket, 1ull | TICKET_FIN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+    if (!fin) return;
+    // ---- the finisher zeroes the landed words: every report of the pass is in (its own completed the last group).  Queue, started
+    // and ticket words stay: servers still claim slots behind it, the poisoner still reads the counts -- those are the last leaver's.
+    if (lane < (int)n_groups) st_dev(A.sync + (size_t)PASS_SYNC_STRIDE * lane + LAND_WORD, 0ull);
+    if (lane == 0) st_dev(root + LAND_ROOT, 0ull);
+    // its ticket, second level; should it be the wave that leaves last, the cleaning is its job
+    if (lane == 0 && (unsigned int)tg_old == g_tiles - 1u) last = ticket_root(root, tg_old, false, false, true, n_groups, fin_seen);
+    stamp_wave();
+    last = __builtin_amdgcn_readfirstlane(last);
+    if (!last) return;
+    if (last == 3 && dbg_arg && lane == 0) atomicAdd(&dbg_arg[(1 << 19) - 16], 1ull);
+    clean_sync();
 }
 
 // Throughput variant of the pass, used while several ICP loops of the process are in flight: waves that wait for work buy
@@ -2096,7 +2219,10 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
     if (fused) {
         void* dp = nullptr;
         if (hipHostGetDevicePointer(&dp, ctx->h_state, 0) == hipSuccess) pa.host_block = (unsigned long long*)dp;
-        *h_flag = 0ull;   // (the stream is idle: the previous call waited for its own flag)
+        // (nothing in flight stores to the landing block: the previous call waited for its own flag, the last store of the one
+        // wave per pass that writes there; what may still be draining on the stream -- the waves leaving that pass, no-op passes
+        // behind a stop -- touches the call's scratch only)
+        *h_flag = 0ull;
         h_flag[-1] = 0ull;   // "the call's first kernel runs"
     }
     hipError_t e = hipSuccess;
@@ -2207,7 +2333,8 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
             prev = end;
         }
         ctx->pass_log_n = np;
-        // the loop's duration on the device, from the kernels' own clock: first kernel of the call .. end of its last pass
+        // the loop's duration on the device, from the kernels' own clock: first kernel of the call .. end of its last pass (the
+        // finisher's stamp: in a one-launch pass the waiters are still leaving then, the kernel ends a microsecond or two later)
         ctx->loop_dev_ms = np > 0 ? 1e-5 * (double)(unsigned int)(lg[np - 1] - lg[3 * PCR_ICP_MAX_LOG]) : 0.0;
     }
     ctx->pass_host_us[3] = h_us(h_t0);   // the whole loop on the host

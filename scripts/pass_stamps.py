@@ -70,3 +70,38 @@ print("items per group min/median/max", int(it_g.min()), int(np.median(it_g)), i
       "| last tile end per group min/max %.1f %.1f" % (last_tile_g.min(), last_tile_g.max()))
 busy = w[:, 4] > 0
 print("waves that served items: exit us pct 50/90/99/max", pc(us(w[busy, 3])), " idle ones:", pc(us(w[~busy, 3])))
+# ---- when the last contribution to the accumulators LANDED (where a finish by the last lander starts), from the stamps above.
+# Tiles: "moments in" is taken behind the reply of the done-add, which was issued in front of the 19 moment atomics: their
+# acknowledgement follows within one round trip.  Items: pass_serve_item stamps its start (shader clock / 16, from the serving wave's
+# start) and its duration in its slot, group + 32 * index; a group's slots of THIS pass are the first `items served by the group`
+# ones (the block is not zeroed per pass).  The shader clock is calibrated against the real-time stamps of the tiles (per block:
+# longest start -> moments-in span in both clocks); the serving wave is not recorded, so its start is taken as the median one.
+RT_US = 1.4   # one returning atomic inside the launch (scripts/atomic_rt.hip: 0.7 us unloaded, about 1.4 loaded)
+blk_cyc = buf[:nblk * 4].reshape(nblk, 4)[:, 0].astype(np.float64)
+blk_rt = (w[:, 2] - w[:, 0]).reshape(nblk, 4).max(axis=1).astype(np.float64)
+ok = (blk_cyc > 0) & (blk_rt > 0)
+cyc_per_us = float(np.median(blk_cyc[ok] / blk_rt[ok])) * 100.0 if ok.any() else 0.0
+item_end = []
+full = buf[(1 << 17):(1 << 17) + 240000].reshape(-1, 4)
+for g in range(32):
+    for k in range(int(it_g[g])):
+        e = full[g + 32 * k]
+        if g + 32 * k < 59999 and e[0] > 0 and cyc_per_us > 0:
+            item_end.append((float(int(e[1]) & 0xffffffff) * 16.0 + float(e[0])) / cyc_per_us)
+start_med = float(np.median(us(w[:, 0])))
+# (the wave that writes the poison takes its "moments in" stamp behind those stores: a tile's span is capped at the 99th percentile)
+span = w[:, 2] - w[:, 1]
+last_tile_in = float(us(w[:, 1] + np.minimum(span, int(np.percentile(span, 99)))).max())
+last_item_in = start_med + max(item_end) if item_end else 0.0
+first_sum = (int(buf[(1 << 19) - 4]) - t0) / 100.0
+print("shader clock %.0f cycles per us | last tile's moments issued %.2f us, last item's %.2f us (%d items stamped) -> last contribution acknowledged about %.2f us (+ one round trip of %.1f us); the finishing wave's first sum in %.2f us"
+      % (cyc_per_us, last_tile_in, last_item_in, len(item_end), max(last_tile_in, last_item_in) + RT_US, RT_US, first_sum))
+# ---- who finished (a library with the landed counts, PCR_PASS_DIAG build; zeros with an older one)
+kind = int(buf[(1 << 19) - 6])
+if kind:
+    names = {1: "the last lander, a tile wave", 2: "the last lander, an item server", 3: "the last leaver (fall-back)"}
+    print("finished by %s: chosen at %.2f us, first sum in %.2f, Procrustes done %.2f, state written %.2f us; last exit (ticket) %.2f us"
+          % (names.get(kind, "?"), (int(buf[(1 << 19) - 5]) - t0) / 100.0, first_sum, (int(buf[(1 << 19) - 2]) - t0) / 100.0, (int(buf[(1 << 19) - 1]) - t0) / 100.0, float(us(w[:, 7]).max())))
+else:
+    print("finished by the last leaver (no landed counts in this library); last exit (ticket) %.2f us" % float(us(w[:, 7]).max()))
+print("passes finished by the last lander %d, by the last leaver %d, passes with a give-up %d (whole process)" % (int(buf[(1 << 19) - 15]), int(buf[(1 << 19) - 14]), int(buf[(1 << 19) - 16])))
