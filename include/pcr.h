@@ -787,6 +787,46 @@ PCR_API int pcr_pn2_sa_mlp_max(void* stream, int b, int n, int m, int nsample, i
                                const float* const* weights /* host, n_layers device pointers */,
                                const float* const* biases /* host, n_layers device pointers */, float* out, long long out_batch_stride);
 
+/* Feature propagation for inference, fused: the three-point interpolation of the known points' features, the concatenation with the
+ * points' own (skip) features and the per-point shared MLP (batch norm folded into the weights by the caller) in one kernel; neither
+ * the interpolated tensor nor the (b, c_known + c_skip, n) concatenation nor any layer's intermediate is stored.  Same calling rules
+ * as pcr_pn2_sa_mlp_max: the caller's device memory and stream, no context, no allocation, no wait; `widths`, `weights` and `biases`
+ * are HOST arrays of n_layers entries read during the call, weights[l] (widths[l], K_l) row-major and biases[l] (widths[l]) device
+ * pointers, K_l = widths[l-1].  The neighbour search is not part of it: idx and weight are pcr_pn2_three_nn's indices and the
+ * caller's normalised inverse distances, as for pcr_pn2_three_interpolate.  Both feature tensors are POINT-major.
+ * Contract.  All arithmetic is binary32, no contraction in the VALU parts.
+ *   - Row layout.  The row of point (bi, i) has K_0 = c_known + c_skip >= 1 entries.  For k < c_known:
+ *     ((p0*w0) + (p1*w1)) + (p2*w2) with pj = known_feats[bi, idx[bi,i,j], k] and wj = weight[bi,i,j], the expression and order of
+ *     pcr_pn2_three_interpolate.  Then follow skip_feats[bi, i, 0:c_skip], without padding between the two parts.  c_known == 0 is
+ *     legal and makes the call a plain per-point shared MLP (known_feats, idx and weight are then not read and may be NULL).
+ *   - Layer l computes acc = bias_l[j], then for k = 0 .. K_l-1 in ascending order acc = fmaf(x[k], W_l[j,k], acc): one chain per
+ *     output, no split over k, exactly as for pcr_pn2_sa_mlp_max.  After every layer but the last, and after the last one when
+ *     relu_last != 0: y[j] = acc > 0 ? acc : +0.  With relu_last == 0 the last layer stores acc + (+0.0f): an accumulator of -0 is
+ *     stored as +0, for every K.
+ *   - out[bi, j, i] (b, widths[n_layers-1], n) is stored once: no two workgroups share a row, there are no atomics, `out` needs no
+ *     zeroing and elements outside the addressed ones are not touched.  The result is bitwise repeatable.  A tile row that stands
+ *     for no point is a copy of the last real row and is never stored.
+ *   - Inputs must be finite and indices in range; neither is validated, as for the other ops.
+ *   - PCR_OK for a normal call; PCR_E_INVALID for a negative size, K_0 < 1, n_layers < 1, a width below 1, m < 1 with c_known > 0
+ *     and a non-empty output, or a NULL pointer where data is needed; PCR_E_UNSUPPORTED, before any launch, for a shape the kernel
+ *     declines; PCR_E_HIP for a failed launch.  An empty output (b == 0 or n == 0) returns PCR_OK and launches nothing.
+ *   - Supported: 1 to PCR_PN2_FP_MAX_LAYERS layers, every width at most PCR_PN2_FP_MAX_WIDTH, K_0 at most PCR_PN2_FP_MAX_K0, at most
+ *     2^31 - 1 workgroups of 64 rows.  The on-chip budget is the set-abstraction kernel's: a 64-row tile of one layer's activations
+ *     in LDS (64 x 257 floats) beside a 32-column stage of the weights (256 x 33) and of the rows (64 x 33) and 3 KiB of per-row
+ *     words, 109 KiB of 160, and the tile's accumulators in registers.  K_0 is streamed 32 columns at a time.  This covers every
+ *     decoder module and the head of the reference's segmentation networks except the two deepest modules of the multi-scale one
+ *     (widths 512).                                                                                                               */
+#define PCR_PN2_FP_MAX_LAYERS 3
+#define PCR_PN2_FP_MAX_WIDTH 256
+#define PCR_PN2_FP_MAX_K0 1024
+PCR_API int pcr_pn2_fp_mlp(void* stream, int b, int n, int m, int c_known, int c_skip,
+                           const float* known_feats /* b,m,c_known point-major; NULL iff c_known == 0 */,
+                           const int32_t* idx /* b,n,3; NULL iff c_known == 0 */, const float* weight /* b,n,3; NULL iff c_known == 0 */,
+                           const float* skip_feats /* b,n,c_skip point-major; NULL iff c_skip == 0 */, int n_layers,
+                           const int* widths /* host, n_layers */, const float* const* weights /* host, n_layers device pointers */,
+                           const float* const* biases /* host, n_layers device pointers */, int relu_last,
+                           float* out /* b, widths[n_layers-1], n */);
+
 /* ----------------------------------------------------------- object batches
  * The stage between DBSCAN's labels and the classifier's input: `preprocess` of Final_Project/scripts/detect.py:269-354, whose
  * resampling step also builds the training set (generating-training-set.py:186-194).  All arithmetic is binary64 on the stored

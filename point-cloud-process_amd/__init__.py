@@ -94,7 +94,7 @@ __version__ = "0.1.0"
 # The PointNet++ ops are torch modules and autograd functions: they come in on first use, so that importing the package does not
 # import torch (see PCR_NO_TORCH_PRELOAD in _lib.py).
 _POINTNET2_EXPORTS = ("pointnet2_ops", "pointnet2_utils", "pointnet2_modules", "furthest_point_sample_np", "pointnet2_models",
-                      "PointNet2ClassificationSSG", "PointNet2ClassificationMSG")
+                      "PointNet2ClassificationSSG", "PointNet2ClassificationMSG", "PointNet2SemSegSSG", "PointNet2SemSegMSG")
 
 
 def __getattr__(name):

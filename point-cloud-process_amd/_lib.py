@@ -376,6 +376,9 @@ SIGNATURES = {
     # (stream, b, n, m, nsample, c_feat, use_xyz, xyz, new_xyz, feats, idx, n_layers, host widths, host weight / bias pointer arrays, out, stride)
     "pcr_pn2_sa_mlp_max": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int),
                                      C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, C.c_longlong]),
+    # (stream, b, n, m, c_known, c_skip, known_feats, idx, weight, skip_feats, n_layers, host widths, host weight / bias pointer arrays, relu_last, out)
+    "pcr_pn2_fp_mlp": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int),
+                                 C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, _vp]),
     # object batches: (ctx, objects handle, host arrays...); the pack's last argument is the address of the caller's device tensor
     "pcr_objects_build": (C.c_int, [_vp, _vp, _ip, C.c_int32, C.POINTER(_vp)]),
     "pcr_objects_free": (C.c_int, [_vp, _vp]),

@@ -32,18 +32,36 @@ def fold_shared_mlp(mlp):
     the batch's statistics)."""
     if mlp.training:
         raise ValueError("fold_shared_mlp needs a module in eval mode: in training mode batch norm uses the batch's statistics")
-    layers = list(mlp)
+    folded, relu_last = _fold_layers(list(mlp), nn.Conv2d, nn.BatchNorm2d)
+    if not relu_last:
+        raise ValueError("every layer of the shared MLP must end in a ReLU")
+    return folded
+
+
+def fold_pointwise_head(head):
+    """``fold_shared_mlp`` for a per-point head of ``Conv1d`` (kernel size 1), ``BatchNorm1d``, ``ReLU`` and ``Dropout`` layers in eval
+    mode (where dropout is the identity and is skipped) -> ``(layers, relu_last)``: the last layer may come without a ReLU, every
+    other one must have it."""
+    if head.training:
+        raise ValueError("fold_pointwise_head needs a module in eval mode: in training mode batch norm uses the batch's statistics")
+    return _fold_layers([layer for layer in head if not isinstance(layer, nn.Dropout)], nn.Conv1d, nn.BatchNorm1d)
+
+
+def _fold_layers(layers, conv_type, bn_type):
     folded = []
     i = 0
+    relu = True
     with torch.no_grad():
         while i < len(layers):
             conv = layers[i]
-            if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (1, 1) or conv.groups != 1:
+            if not isinstance(conv, conv_type) or any(k != 1 for k in conv.kernel_size) or conv.groups != 1:
                 raise ValueError(f"layer {i} of the shared MLP is not a 1x1 convolution: {conv!r}")
+            if not relu:
+                raise ValueError("every layer of the shared MLP must end in a ReLU")
             i += 1
             W = conv.weight.detach().to(torch.float64).reshape(conv.out_channels, conv.in_channels)
             bias = conv.bias.detach().to(torch.float64) if conv.bias is not None else torch.zeros(conv.out_channels, dtype=torch.float64, device=W.device)
-            if i < len(layers) and isinstance(layers[i], nn.BatchNorm2d):
+            if i < len(layers) and isinstance(layers[i], bn_type):
                 bn = layers[i]
                 i += 1
                 if bn.running_var is None or bn.running_mean is None:
@@ -54,12 +72,30 @@ def fold_shared_mlp(mlp):
                 beta = bn.bias.detach().to(torch.float64) if bn.bias is not None else torch.zeros_like(s)
                 W = W * s[:, None]
                 bias = beta - bn.running_mean.detach().to(torch.float64) * s + (bias * s if conv.bias is not None else 0.0)
-            if i < len(layers) and isinstance(layers[i], nn.ReLU):
+            relu = i < len(layers) and isinstance(layers[i], nn.ReLU)
+            if relu:
                 i += 1
-            else:
-                raise ValueError("every layer of the shared MLP must end in a ReLU")
             folded.append((W.to(torch.float32).contiguous(), bias.to(torch.float32).contiguous()))
-    return folded
+    return folded, relu
+
+
+class _FoldedCache:
+    """``fold(module)`` kept per key until one of the module's parameters or buffers is written to, replaced or moved."""
+
+    def __init__(self, fold):
+        self._fold = fold
+        self._kept = {}
+
+    def get(self, key, module):
+        try:
+            stamp = tuple((t._version, t.data_ptr()) for t in list(module.parameters()) + list(module.buffers()))
+        except RuntimeError:     # tensors made in inference mode keep no version: fold every time
+            stamp = None
+        kept = self._kept.get(key)
+        if kept is None or stamp is None or kept[0] != stamp:
+            kept = (stamp, self._fold(module))
+            self._kept[key] = kept
+        return kept[1]
 
 
 class _PointnetSAModuleBase(nn.Module):
@@ -68,20 +104,11 @@ class _PointnetSAModuleBase(nn.Module):
         self.npoint = None
         self.groupers = None
         self.mlps = None
-        self._folded = {}
+        self._folded = _FoldedCache(fold_shared_mlp)
 
     def _folded_mlp(self, scale):
         """fold_shared_mlp of one scale, kept until one of its parameters or buffers is written to, replaced or moved."""
-        mlp = self.mlps[scale]
-        try:
-            stamp = tuple((t._version, t.data_ptr()) for t in list(mlp.parameters()) + list(mlp.buffers()))
-        except RuntimeError:     # tensors made in inference mode keep no version: fold every time
-            stamp = None
-        kept = self._folded.get(scale)
-        if kept is None or stamp is None or kept[0] != stamp:
-            kept = (stamp, fold_shared_mlp(mlp))
-            self._folded[scale] = kept
-        return kept[1]
+        return self._folded.get(scale, self.mlps[scale])
 
     def fused_forward(self, xyz: torch.Tensor, features: Optional[torch.Tensor]) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
         """``forward`` for inference (eval mode, grad disabled; anything else raises): the same sampling and ball query, then per scale
@@ -167,6 +194,46 @@ class PointnetFPModule(nn.Module):
     def __init__(self, mlp, bn=True):
         super().__init__()
         self.mlp = build_shared_mlp(mlp, bn=bn)
+        self._folded = _FoldedCache(fold_shared_mlp)
+
+    def fused_forward(self, unknown, known, unknow_feats, known_feats):
+        """``forward`` for inference (eval mode, grad disabled; anything else raises): the same three_nn and the same weights, then ONE
+        kernel (pointnet2_utils.propagated_mlp) that interpolates, joins the unknown points' own features and runs the shared MLP with
+        its batch norm folded in; neither the interpolated tensor nor the concatenation nor a layer's intermediate is stored.
+        ``known is None`` (the expand branch), a shape the kernel declines and a shape measured slower than ``forward``
+        (``_kernel_takes``) go through ``forward``.  Every output is one binary32 fmaf chain per layer (include/pcr.h), so the values
+        differ from ``forward``'s by rounding only."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("fused_forward is for inference: call it on a module in eval() mode under torch.no_grad()")
+        if known is None or not self._kernel_takes():
+            return self.forward(unknown, known, unknow_feats, known_feats)
+        dist, idx = pointnet2_utils.three_nn(unknown, known)
+        recip = 1.0 / (dist + 1e-8)
+        weight = recip / torch.sum(recip, dim=2, keepdim=True)
+        folded = self._folded.get(0, self.mlp)
+        try:
+            return pointnet2_utils.propagated_mlp(known_feats.transpose(1, 2).contiguous(), idx, weight,
+                                                  None if unknow_feats is None else unknow_feats.transpose(1, 2).contiguous(),
+                                                  [w for w, _ in folded], [b for _, b in folded])
+        except _lib.PcrError as err:
+            if err.status != _lib.PCR_E_UNSUPPORTED:
+                raise
+        return self._joined_mlp(pointnet2_utils.three_interpolate(known_feats, idx, weight), unknow_feats)     # forward's torch ops
+
+    # Above 128 channels the kernel keeps one workgroup of four waves per compute unit, and a workgroup walks its K_0 columns 32 at a
+    # time in one serial chain: measured at B = 8 (profiles/fp_fused_bench.json "routed", DESIGN.md 3.6.13), [608, 256, 256] on 1024
+    # points took 0.256 ms against forward's 0.190 and [768, 256, 256] on 64 points 0.213 against 0.184, while [384, 256, 256] and
+    # [320, 256, 128] were faster than forward.
+    FUSED_MAX_K0_WIDE = 384
+
+    def _kernel_takes(self):
+        """Whether fused_forward hands this module's shape to the kernel: within the kernel's limits (checked here, so that a module
+        it declines costs nothing beyond forward), and not one of the shapes measured slower than forward."""
+        convs = [layer for layer in self.mlp if isinstance(layer, nn.Conv2d)]
+        k0, widest = convs[0].in_channels, max(c.out_channels for c in convs)
+        if len(convs) > pointnet2_utils.FP_MLP_MAX_LAYERS or widest > pointnet2_utils.FP_MLP_MAX_WIDTH or k0 > pointnet2_utils.FP_MLP_MAX_K0:
+            return False
+        return widest <= 128 or k0 <= self.FUSED_MAX_K0_WIDE
 
     def forward(self, unknown, known, unknow_feats, known_feats):
         """unknown (B, n, 3), known (B, m, 3) or None, unknow_feats (B, C1, n) or None, known_feats (B, C2, m) -> (B, mlp[-1], n)."""
@@ -177,5 +244,8 @@ class PointnetFPModule(nn.Module):
             interpolated = pointnet2_utils.three_interpolate(known_feats, idx, weight)
         else:
             interpolated = known_feats.expand(*known_feats.shape[:2], unknown.size(1))
+        return self._joined_mlp(interpolated, unknow_feats)
+
+    def _joined_mlp(self, interpolated, unknow_feats):
         new_features = interpolated if unknow_feats is None else torch.cat([interpolated, unknow_feats], dim=1)
         return self.mlp(new_features.unsqueeze(-1)).squeeze(-1)

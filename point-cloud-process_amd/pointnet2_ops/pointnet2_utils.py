@@ -398,6 +398,80 @@ def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True
     return out
 
 
+FP_MLP_MAX_LAYERS, FP_MLP_MAX_WIDTH, FP_MLP_MAX_K0 = 3, 256, 1024     # PCR_PN2_FP_MAX_LAYERS / _WIDTH / _K0 of include/pcr.h
+
+
+def propagated_mlp(known_feats_t, idx, weight, skip_feats_t, weights, biases, relu_last=True, out=None):
+    """Feature propagation for inference in one kernel (include/pcr.h, pcr_pn2_fp_mlp): per point the row of its interpolated features
+    -- ((p0*w0) + (p1*w1)) + (p2*w2) over its three known points, three_interpolate's expression -- followed by its own (skip)
+    features, through the layers ``relu(W x + b)``; the last layer without the ReLU when relu_last is false.  Neither the interpolated
+    tensor nor the concatenation nor a layer's intermediate is stored.
+
+    known_feats_t (B, m, C2) POINT-major, idx (B, n, 3) int32 (three_nn's) and weight (B, n, 3): all three given or all three None
+    (then the call is a plain per-point shared MLP on skip_feats_t); skip_feats_t (B, n, C1) POINT-major or None; weights[l]
+    (width_l, K_l) and biases[l] (width_l,) float32 with K_0 = C2 + C1 and K_l = width_(l-1) -> (B, width_last, n).  `out`: a
+    contiguous (B, width_last, n) float32 tensor to write into instead; it is returned.
+
+    Not differentiable: an input that requires grad while grad is enabled raises ValueError.  A shape the kernel declines raises
+    PcrError with status PCR_E_UNSUPPORTED and has launched nothing."""
+    weights, biases = list(weights), list(biases)
+    if len(weights) != len(biases) or not weights:
+        raise ValueError("weights and biases must be lists of the same length, one entry per layer (at least one)")
+    interp = (known_feats_t, idx, weight)
+    if any(t is None for t in interp) and not all(t is None for t in interp):
+        raise ValueError("known_feats_t, idx and weight must be given together or all be None")
+    has_known = known_feats_t is not None
+    if not has_known and skip_feats_t is None:
+        raise ValueError("propagated_mlp needs known_feats_t (with idx and weight) or skip_feats_t")
+    specs = []
+    if has_known:
+        specs += [(known_feats_t, "known_feats_t", f32, ("B", "m", None)), (idx, "idx", i32, ("B", "n", 3)), (weight, "weight", f32, ("B", "n", 3))]
+    if skip_feats_t is not None:
+        specs.append((skip_feats_t, "skip_feats_t", f32, ("B", "n", None)))
+    for l, (w, bias) in enumerate(zip(weights, biases)):
+        specs += [(w, f"weights[{l}]", f32, (f"w{l}", f"k{l}")), (bias, f"biases[{l}]", f32, (f"w{l}",))]
+    _check(*specs, device=False)
+    c_known = known_feats_t.shape[2] if has_known else 0
+    c_skip = skip_feats_t.shape[2] if skip_feats_t is not None else 0
+    k = c_known + c_skip
+    if k < 1:
+        raise ValueError("propagated_mlp needs at least one feature channel")
+    for l, w in enumerate(weights):
+        if w.shape[1] != k:
+            raise ValueError(f"weights[{l}] must have {k} entries along axis 1, not {w.shape[1]}")
+        if w.shape[0] < 1:
+            raise ValueError(f"weights[{l}] must have at least one row")
+        k = w.shape[0]
+    anchor = specs[0][0]
+    B = anchor.shape[0]
+    n = idx.shape[1] if has_known else skip_feats_t.shape[1]
+    m = known_feats_t.shape[1] if has_known else 0
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != f32 or tuple(out.shape) != (B, k, n):
+            raise ValueError(f"out must be a float32 tensor of shape {(B, k, n)}")
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+    tensors = [t for t, *_ in specs] + ([out] if out is not None else [])
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError("propagated_mlp is not differentiable: call it under torch.no_grad() or on tensors that do not require grad")
+    if has_known and B and n and m == 0:
+        raise ValueError("known_feats_t has no points to interpolate from")
+    _check(*specs)
+    if out is not None and out.device != anchor.device:
+        raise ValueError(f"out is on {out.device}, {specs[0][1]} on {anchor.device}")
+    if out is None:
+        out = torch.empty((B, k, n), dtype=f32, device=anchor.device)
+    n_layers = len(weights)
+    C = _lib.C
+    widths = (C.c_int * n_layers)(*[w.shape[0] for w in weights])
+    wptr = (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights])
+    bptr = (C.c_void_p * n_layers)(*[t.data_ptr() for t in biases])
+    _launch(anchor, "pcr_pn2_fp_mlp", B, n, m, c_known, c_skip, known_feats_t.data_ptr() if has_known else None,
+            idx.data_ptr() if has_known else None, weight.data_ptr() if has_known else None,
+            skip_feats_t.data_ptr() if skip_feats_t is not None else None, n_layers, widths, wptr, bptr, 1 if relu_last else 0, out.data_ptr())
+    return out
+
+
 class QueryAndGroup(nn.Module):
     """Ball query around every centre, then the neighbours' coordinates relative to the centre (and their features)."""
 
