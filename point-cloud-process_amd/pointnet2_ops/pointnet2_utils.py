@@ -337,6 +337,36 @@ class BallQuery(Function):
 ball_query = BallQuery.apply
 
 
+def _layer_specs(weights, biases):
+    """The layer lists of grouped_mlp_max / propagated_mlp as lists, checked for their lengths, and one _check spec per tensor."""
+    weights, biases = list(weights), list(biases)
+    if len(weights) != len(biases) or not weights:
+        raise ValueError("weights and biases must be lists of the same length, one entry per layer (at least one)")
+    specs = []
+    for l, (w, bias) in enumerate(zip(weights, biases)):
+        specs += [(w, f"weights[{l}]", f32, (f"w{l}", f"k{l}")), (bias, f"biases[{l}]", f32, (f"w{l}",))]
+    return weights, biases, specs
+
+
+def _layer_chain(weights, biases, k):
+    """K_0 = k and K_l = width_(l-1) along the layers (which have passed _check) -> the last width and (n_layers, widths, weights,
+    biases) as the C entry points take them."""
+    for l, w in enumerate(weights):
+        if w.shape[1] != k:
+            raise ValueError(f"weights[{l}] must have {k} entries along axis 1, not {w.shape[1]}")
+        if w.shape[0] < 1:
+            raise ValueError(f"weights[{l}] must have at least one row")
+        k = w.shape[0]
+    n_layers, C = len(weights), _lib.C
+    return k, (n_layers, (C.c_int * n_layers)(*[w.shape[0] for w in weights]), (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights]),
+               (C.c_void_p * n_layers)(*[t.data_ptr() for t in biases]))
+
+
+def _not_differentiable(name, specs, out):
+    if torch.is_grad_enabled() and any(t.requires_grad for t, *_ in specs + ([(out,)] if out is not None else [])):
+        raise ValueError(f"{name} is not differentiable: call it under torch.no_grad() or on tensors that do not require grad")
+
+
 def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True, out=None):
     """Set abstraction for inference in one kernel (include/pcr.h, pcr_pn2_sa_mlp_max): per centre the rows of its ball -- relative
     coordinates (use_xyz), then the point's features -- through the layers ``relu(W x + b)`` and the maximum over the ball; the grouped
@@ -349,25 +379,17 @@ def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True
 
     Not differentiable: an input that requires grad while grad is enabled raises ValueError.  A shape the kernel declines raises
     PcrError with status PCR_E_UNSUPPORTED and has launched nothing."""
-    weights, biases = list(weights), list(biases)
-    if len(weights) != len(biases) or not weights:
-        raise ValueError("weights and biases must be lists of the same length, one entry per layer (at least one)")
+    weights, biases, layer_specs = _layer_specs(weights, biases)
     specs = [(xyz, "xyz", f32, ("B", "N", 3)), (new_xyz, "new_xyz", f32, ("B", "m", 3)), (idx, "idx", i32, ("B", "m", None))]
     if features_t is not None:
         specs.append((features_t, "features_t", f32, ("B", "N", None)))
-    for l, (w, bias) in enumerate(zip(weights, biases)):
-        specs += [(w, f"weights[{l}]", f32, (f"w{l}", f"k{l}")), (bias, f"biases[{l}]", f32, (f"w{l}",))]
+    specs += layer_specs
     _check(*specs, device=False)
     c_feat = 0 if features_t is None else features_t.shape[2]
     k = (3 if use_xyz else 0) + c_feat
     if k < 1:
         raise ValueError("grouped_mlp_max without features needs use_xyz")
-    for l, w in enumerate(weights):
-        if w.shape[1] != k:
-            raise ValueError(f"weights[{l}] must have {k} entries along axis 1, not {w.shape[1]}")
-        if w.shape[0] < 1:
-            raise ValueError(f"weights[{l}] must have at least one row")
-        k = w.shape[0]
+    k, layer_args = _layer_chain(weights, biases, k)
     B, N, _ = xyz.shape
     _, npoint, nsample = idx.shape
     if out is not None:
@@ -375,9 +397,7 @@ def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True
             raise ValueError(f"out must be a float32 tensor of shape {(B, k, npoint)}")
         if B and k and npoint and (out.stride(2) != 1 or out.stride(1) != npoint or (B > 1 and out.stride(0) < k * npoint)):
             raise ValueError("out must be contiguous in its last two axes, with a batch stride that keeps the batches apart")
-    tensors = [t for t, *_ in specs] + ([out] if out is not None else [])
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise ValueError("grouped_mlp_max is not differentiable: call it under torch.no_grad() or on tensors that do not require grad")
+    _not_differentiable("grouped_mlp_max", specs, out)
     if B and npoint and nsample < 1:
         raise ValueError("idx has no samples per centre")
     if B and npoint and N == 0:
@@ -387,13 +407,8 @@ def grouped_mlp_max(xyz, new_xyz, features_t, idx, weights, biases, use_xyz=True
         raise ValueError(f"out is on {out.device}, xyz on {xyz.device}")
     if out is None:
         out = torch.empty((B, k, npoint), dtype=f32, device=xyz.device)
-    n_layers = len(weights)
-    C = _lib.C
-    widths = (C.c_int * n_layers)(*[w.shape[0] for w in weights])
-    wptr = (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights])
-    bptr = (C.c_void_p * n_layers)(*[t.data_ptr() for t in biases])
     _launch(xyz, "pcr_pn2_sa_mlp_max", B, N, npoint, nsample, c_feat, 1 if use_xyz else 0, xyz.data_ptr(), new_xyz.data_ptr(),
-            features_t.data_ptr() if features_t is not None else None, idx.data_ptr(), n_layers, widths, wptr, bptr, out.data_ptr(),
+            features_t.data_ptr() if features_t is not None else None, idx.data_ptr(), *layer_args, out.data_ptr(),
             out.stride(0) if B > 1 else k * npoint)
     return out
 
@@ -414,9 +429,7 @@ def propagated_mlp(known_feats_t, idx, weight, skip_feats_t, weights, biases, re
 
     Not differentiable: an input that requires grad while grad is enabled raises ValueError.  A shape the kernel declines raises
     PcrError with status PCR_E_UNSUPPORTED and has launched nothing."""
-    weights, biases = list(weights), list(biases)
-    if len(weights) != len(biases) or not weights:
-        raise ValueError("weights and biases must be lists of the same length, one entry per layer (at least one)")
+    weights, biases, layer_specs = _layer_specs(weights, biases)
     interp = (known_feats_t, idx, weight)
     if any(t is None for t in interp) and not all(t is None for t in interp):
         raise ValueError("known_feats_t, idx and weight must be given together or all be None")
@@ -428,20 +441,14 @@ def propagated_mlp(known_feats_t, idx, weight, skip_feats_t, weights, biases, re
         specs += [(known_feats_t, "known_feats_t", f32, ("B", "m", None)), (idx, "idx", i32, ("B", "n", 3)), (weight, "weight", f32, ("B", "n", 3))]
     if skip_feats_t is not None:
         specs.append((skip_feats_t, "skip_feats_t", f32, ("B", "n", None)))
-    for l, (w, bias) in enumerate(zip(weights, biases)):
-        specs += [(w, f"weights[{l}]", f32, (f"w{l}", f"k{l}")), (bias, f"biases[{l}]", f32, (f"w{l}",))]
+    specs += layer_specs
     _check(*specs, device=False)
     c_known = known_feats_t.shape[2] if has_known else 0
     c_skip = skip_feats_t.shape[2] if skip_feats_t is not None else 0
     k = c_known + c_skip
     if k < 1:
         raise ValueError("propagated_mlp needs at least one feature channel")
-    for l, w in enumerate(weights):
-        if w.shape[1] != k:
-            raise ValueError(f"weights[{l}] must have {k} entries along axis 1, not {w.shape[1]}")
-        if w.shape[0] < 1:
-            raise ValueError(f"weights[{l}] must have at least one row")
-        k = w.shape[0]
+    k, layer_args = _layer_chain(weights, biases, k)
     anchor = specs[0][0]
     B = anchor.shape[0]
     n = idx.shape[1] if has_known else skip_feats_t.shape[1]
@@ -451,9 +458,7 @@ def propagated_mlp(known_feats_t, idx, weight, skip_feats_t, weights, biases, re
             raise ValueError(f"out must be a float32 tensor of shape {(B, k, n)}")
         if not out.is_contiguous():
             raise ValueError("out must be contiguous")
-    tensors = [t for t, *_ in specs] + ([out] if out is not None else [])
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
-        raise ValueError("propagated_mlp is not differentiable: call it under torch.no_grad() or on tensors that do not require grad")
+    _not_differentiable("propagated_mlp", specs, out)
     if has_known and B and n and m == 0:
         raise ValueError("known_feats_t has no points to interpolate from")
     _check(*specs)
@@ -461,14 +466,9 @@ def propagated_mlp(known_feats_t, idx, weight, skip_feats_t, weights, biases, re
         raise ValueError(f"out is on {out.device}, {specs[0][1]} on {anchor.device}")
     if out is None:
         out = torch.empty((B, k, n), dtype=f32, device=anchor.device)
-    n_layers = len(weights)
-    C = _lib.C
-    widths = (C.c_int * n_layers)(*[w.shape[0] for w in weights])
-    wptr = (C.c_void_p * n_layers)(*[w.data_ptr() for w in weights])
-    bptr = (C.c_void_p * n_layers)(*[t.data_ptr() for t in biases])
     _launch(anchor, "pcr_pn2_fp_mlp", B, n, m, c_known, c_skip, known_feats_t.data_ptr() if has_known else None,
             idx.data_ptr() if has_known else None, weight.data_ptr() if has_known else None,
-            skip_feats_t.data_ptr() if skip_feats_t is not None else None, n_layers, widths, wptr, bptr, 1 if relu_last else 0, out.data_ptr())
+            skip_feats_t.data_ptr() if skip_feats_t is not None else None, *layer_args, 1 if relu_last else 0, out.data_ptr())
     return out
 
 

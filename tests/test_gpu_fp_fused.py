@@ -150,6 +150,31 @@ def test_reference_specs(u, spec):
     check_bits(u, case, make_layers(rng, c_known + c_skip, widths), relu_last=c_known > 0)       # the head is the one without known points and without a last ReLU
 
 
+@pytest.mark.parametrize("k0,widths", [(5, [32]), (33, [64, 130]), (70, [256, 13]), (33, [64, 128])], ids=["5-32", "33-64-130", "70-256-13", "33-64-128"])
+def test_both_kernels_store_the_same_bits_for_the_same_rows(u, k0, widths):
+    """One layer loop (pn2_tile_layers) serves both kernels: the same rows through the same layers come out with the same bits from
+    propagated_mlp without known points and from grouped_mlp_max with balls of one point (use_xyz off, centre i gathers point i), and
+    those are the restatement's.  B = 2, n = 65: the second FP tile straddles the two clouds and the SA unit's last tile is partial.
+    The widest layers 32 / 130 / 256 / 128 take the 64 / 256 / 256 / 128 variants; K_0 is odd, crosses a stage (33, 70), and 130
+    and 13 are no multiples of 32."""
+    import torch
+
+    rng = np.random.default_rng(6600 + k0 + widths[-1])
+    B, n = 2, 65
+    x = rng.standard_normal((B, n, k0)).astype(np.float32)
+    layers = make_layers(rng, k0, widths)
+    fp = run(u, None, None, None, x, layers, relu_last=True)
+    idx = np.ascontiguousarray(np.broadcast_to(np.arange(n, dtype=np.int32)[None, :, None], (B, n, 1)))
+    xyz = dev(np.zeros((B, n, 3), dtype=np.float32))
+    with torch.no_grad():
+        sa = host(u.grouped_mlp_max(xyz, xyz, dev(x), dev(idx), [dev(W) for W, _ in layers], [dev(b) for _, b in layers], use_xyz=False))
+    want = np.ascontiguousarray(chk.mlp_rows(x, layers).transpose(0, 2, 1))
+    assert fp.shape == sa.shape == want.shape == (B, widths[-1], n)
+    assert (want == 0).any() and (want > 0).any()                        # the ReLU clamps some entries and not all
+    assert np.array_equal(fp.view(np.int32), sa.view(np.int32))
+    assert np.array_equal(fp.view(np.int32), want.view(np.int32))
+
+
 def randomise_bn(module, rng):
     """Random batch-norm statistics: scale gamma / sqrt(var + eps) in (0.2, 0.9), shift and mean of size 0.1."""
     import torch
