@@ -285,6 +285,62 @@ PCR_API int pcr_voxel_filter_cloud(pcr_ctx* ctx, const pcr_cloud* in, double lea
 PCR_API int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, double gamma21, double gamma32, double nms_radius,
                     int max_keypoints, double* lambdas_out, int32_t* counts_out, int32_t* keypoints_out, int* n_keypoints_out);
 
+/* ------------------------------------------- PCL keypoints (module PCLKeypoint)
+ * The XYZ detectors of PCLKeypoints/src/keypoints.cpp: keypointHarris3D (pcl::HarrisKeypoint3D, method HARRIS) and keypointIss
+ * (pcl::ISSKeypoint3D without border estimation).  PCL is not part of the build and the reference pins no version of it: the
+ * rules below ARE the definition, restated in NumPy by tests/harris_checks.py; parity with PCL's binary32 output is unpinned.
+ * pcr_iss above follows ISS.py and is another detector (weighted scatter, sequential suppression, a cap).
+ *
+ * Everything is binary64 on the stored coordinates.  N(p_i) = the rows within r of p_i, p_i included; "within r" is
+ * (dx*dx + dy*dy) + dz*dz <= r*r, pcr_iss's predicate.  A cloud whose extent exceeds 2^18 radii: PCR_E_UNSUPPORTED, as pcr_iss.
+ * Per-row arrays are by CALLER ROW, whatever the order of the records on the device (pcr_cloud_reordered).  Sums run in a fixed
+ * order: a call is repeatable to the bit, and its results do not depend on the lay-out of the cloud's records.
+ *
+ * Radius normals (NormalEstimation with setRadiusSearch(r), viewpoint vp; NULL: the origin): with m = |N(p_i)| and x = p_j - p_i,
+ *   cov = sum x x^T / m - mean mean^T, mean = sum x / m; the normal is the unit eigenvector of cov's smallest eigenvalue, flipped so
+ *   that n . (vp - p_i) >= 0; m < 3: all three components NaN.  counts_out[i] = m.
+ *
+ * Harris response, from per-row normals (given, n x 3, rows without a normal hold a non-finite value; or NULL: the radius normals of
+ *   the same radius): for row i with a finite normal, over the k rows of N(p_i) whose normal is finite,
+ *     C = sum n_j n_j^T / k,   trace = Cxx + Cyy + Czz,
+ *     det = Cxx*Cyy*Czz + 2*Cxy*Cxz*Cyz - Cxz*Cxz*Cyy - Cxy*Cxy*Czz - Cyz*Cyz*Cxx,   response = 0.04 + det - 0.04*trace*trace;
+ *   the response is 0 when trace == 0, when k == 0, or when row i has no finite normal.
+ *
+ * Suppression (both detectors, score s): a candidate row is kept iff NO row within the suppression radius has a score strictly
+ *   greater than s_i; ties keep both.  Keypoints are in ascending caller row.
+ *   Harris: candidate iff response_i >= threshold; the suppression radius is `radius`.  nms == 0: every row is a keypoint.
+ *
+ * Refine (params.refine, only together with nms; ignored otherwise): for each kept corner position c, up to 5 rounds of
+ *   A = sum n_j n_j^T, b = sum (n_j n_j^T) p_j over the rows within `radius` of c that have a finite normal; det A != 0: c <- A^-1 b
+ *   (by the adjugate); a round whose squared move is <= 1e-6 is the last.  The keypoint's response stays the unrefined one.
+ *
+ * PCL-rule ISS: S_i = sum (p_j - p_i)(p_j - p_i)^T over N(p_i) within salient_radius, unweighted, not divided; eigenvalues
+ *   e1 >= e2 >= e3; score s_i = e3 if e1 > 0, e2 > 0, e3 >= 0, e2/e1 < gamma21 and e3/e2 < gamma32, else 0.  Row i is a candidate iff
+ *   s_i > 0 and |N(p_i)| within non_max_radius >= min_neighbors; suppression as above over non_max_radius.
+ *   e3_out[i] = s_i (the score: 0 where a rule fails); counts_out[i] = |N(p_i)| within non_max_radius.
+ *
+ * Keypoints: keypoints_out holds up to `capacity` caller rows, *n_keypoints_out their number.  More keypoints than `capacity`:
+ * *n_keypoints_out is the needed number, nothing is written to the per-keypoint arrays and the call returns PCR_E_UNSUPPORTED (the
+ * per-row outputs are complete).  keypoint_response_out (capacity), refined_out (capacity x 3) and rounds_out (capacity; rounds of
+ * the refinement, 1..5) are per keypoint and need keypoints_out.  Every output may be NULL; at least one must be asked for.          */
+typedef struct pcr_harris_params {
+    double radius;      /* keypoints.cpp:253  -> 0.5   */
+    double threshold;   /* keypoints.cpp:254  -> 0.001 */
+    int32_t nms;        /* keypoints.cpp:256  -> 0     */
+    int32_t refine;     /* keypoints.cpp:257  -> 0     */
+    double reserved[4];
+} pcr_harris_params;
+PCR_API void pcr_harris_default_params(pcr_harris_params* p);
+PCR_API int pcr_normals_radius(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, const double* viewpoint /* 3, or NULL */,
+                               double* normals_out /* n*3 */, int32_t* counts_out /* n, or NULL */);
+PCR_API int pcr_harris3d(pcr_ctx* ctx, const pcr_cloud* cloud, const double* normals /* n*3 by row, or NULL */,
+                         const pcr_harris_params* params, double* response_out /* n */, int32_t* counts_out /* n: |N(p_i)| */,
+                         int32_t* keypoints_out, int64_t capacity, int64_t* n_keypoints_out, double* keypoint_response_out,
+                         double* refined_out, int32_t* rounds_out);
+PCR_API int pcr_iss_pcl(pcr_ctx* ctx, const pcr_cloud* cloud, double salient_radius, double non_max_radius, double gamma21,
+                        double gamma32, int min_neighbors, double* e3_out /* n */, int32_t* counts_out /* n */,
+                        int32_t* keypoints_out, int64_t capacity, int64_t* n_keypoints_out);
+
 /* ---------------------------------------------------------- PCA / normals
  * pcr_pca: Pca_and_Voxel_filter/pca_normal.py:10-36 PCA(data, sort=True):
  * eigen-decomposition of np.cov of the cloud (divisor n-1); eigvals_out

@@ -43,6 +43,7 @@ from .global_registration import (  # noqa: F401
     RegistrationResult,
     compute_fpfh_feature,
     estimate_normals_hybrid,
+    estimate_normals_radius,
     execute_global_registration,
     find_matchings,
     prepare_dataset,
@@ -51,6 +52,8 @@ from .global_registration import (  # noqa: F401
     registration_ransac_based_on_feature_matching,
     voxel_down_sample,
 )
+from . import PCLKeypoint  # noqa: F401
+from .PCLKeypoint import keypointHarris3D, keypointIss  # noqa: F401
 from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from . import objects  # noqa: F401

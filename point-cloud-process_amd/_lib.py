@@ -275,6 +275,16 @@ class SpectralResult(C.Structure):
     ]
 
 
+class HarrisParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_double),
+        ("threshold", C.c_double),
+        ("nms", C.c_int32),
+        ("refine", C.c_int32),
+        ("reserved", C.c_double * 4),
+    ]
+
+
 _vp = C.c_void_p
 _dp = C.POINTER(C.c_double)
 _fp = C.POINTER(C.c_float)
@@ -328,6 +338,12 @@ SIGNATURES = {
     "pcr_voxel_filter": (C.c_int, [_vp, _dp, C.c_int64, C.c_double, C.c_int, C.c_uint64, _dp, _lp]),
     "pcr_voxel_filter_cloud": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_uint64, C.POINTER(_vp)]),
     "pcr_iss": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, C.POINTER(C.c_int)]),
+    "pcr_harris_default_params": (None, [C.POINTER(HarrisParams)]),
+    "pcr_normals_radius": (C.c_int, [_vp, _vp, C.c_double, _dp, _dp, _ip]),
+    # (ctx, cloud, normals | NULL, params, response, counts, keypoints, capacity, n_keypoints, keypoint responses, refined, rounds)
+    "pcr_harris3d": (C.c_int, [_vp, _vp, _dp, C.POINTER(HarrisParams), _dp, _ip, _ip, C.c_int64, _lp, _dp, _dp, _ip]),
+    # (ctx, cloud, salient radius, non-max radius, gamma21, gamma32, min_neighbors, scores, counts, keypoints, capacity, n_keypoints)
+    "pcr_iss_pcl": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, C.c_int64, _lp]),
     "pcr_pca": (C.c_int, [_vp, _vp, _dp, _dp, _dp]),
     "pcr_normals": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _ip]),
     "pcr_normals_hybrid": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_int, _dp, _dp]),

@@ -21,39 +21,7 @@
 #include <string>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "pcr_grid_dev.h"
-
-constexpr int IG = 8;  // lanes per point
-
-template <class F>
-__device__ static inline void iss_visit_block(const pcr_grid_view& gv, double ax, double ay, double az, int gl, F& f) {
-    bool clamped = false;
-    const int cx = cell_coord(ax, gv.lo[0], gv.inv_cell0, &clamped);
-    const int cy = cell_coord(ay, gv.lo[1], gv.inv_cell0, &clamped);
-    const int cz = cell_coord(az, gv.lo[2], gv.inv_cell0, &clamped);
-#pragma unroll
-    for (int i = 0; i < (27 + IG - 1) / IG; ++i) {
-        const int n = gl + i * IG;
-        if (n < 27) {
-            const unsigned int nx = (unsigned int)(cx + n % 3 - 1), ny = (unsigned int)(cy + (n / 3) % 3 - 1), nz = (unsigned int)(cz + n / 9 - 1);
-            if (nx <= (unsigned int)PCR_COORD_MAX && ny <= (unsigned int)PCR_COORD_MAX && nz <= (unsigned int)PCR_COORD_MAX) {
-                unsigned int s, e;
-                if (lookup_cell(gv.table[0], gv.mask[0], nx, ny, nz, &s, &e))
-                    for (unsigned int j0 = s; j0 < e; j0 += 4) {   // four records per trip, requested together
-                        pcr_pt rec[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {   // (assigned on every path: conditionally unassigned records become loop-carried registers)
-                            rec[u] = pcr_pt{0.0, 0.0, 0.0, 0};
-                            if (j0 + u < e) rec[u] = gv.pts[j0 + u];
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (j0 + u < e) f(rec[u]);
-                    }
-            }
-        }
-    }
-}
+#include "pcr_ball_visit.h"   // iss_visit_block, IG lanes per point: shared with pcr_harris.hip
 
 __global__ void __launch_bounds__(256) iss_count_kernel(pcr_grid_view gv, long long n, double r2_in, int* __restrict__ counts /* by row id */) {
     const int gl = threadIdx.x % IG;

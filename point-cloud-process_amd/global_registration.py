@@ -17,7 +17,7 @@ from .device import DeviceCloud, TargetIndex, default_context, points_of
 from .registration import PointCloud, read_bin_velodyne
 
 __all__ = [
-    "Feature", "RegistrationResult", "voxel_down_sample", "voxel_down_sample_device", "estimate_normals_hybrid", "compute_fpfh_feature", "find_matchings",
+    "Feature", "RegistrationResult", "voxel_down_sample", "voxel_down_sample_device", "estimate_normals_hybrid", "estimate_normals_radius", "compute_fpfh_feature", "find_matchings",
     "registration_ransac_based_on_feature_matching", "preprocess_point_cloud", "prepare_dataset", "execute_global_registration",
     "ransac_init",
 ]
@@ -188,6 +188,23 @@ def estimate_normals_hybrid(points, radius, max_nn=30, orient=True, viewpoint=(0
     return out
 
 
+def estimate_normals_radius(points, radius, viewpoint=(0.0, 0.0, 0.0), ctx=None, return_counts=False):
+    """pcl::NormalEstimation with setRadiusSearch(radius) (what PCLKeypoint's Harris detector runs first) -> (N,3): the smallest
+    eigenvector of the covariance of ALL rows within ``radius`` (the row itself included; no neighbour cap, unlike the hybrid search
+    above), flipped toward ``viewpoint``; NaN rows where fewer than 3 rows are in the ball.  ``return_counts`` adds the ball sizes."""
+    ctx = ctx or default_context()
+    cloud, own = _cloud(points, ctx)
+    try:
+        out = np.empty((cloud.n, 3), dtype=np.float64)
+        counts = np.empty(cloud.n, dtype=np.int32) if return_counts else None
+        vp = L.as_f64(np.asarray(viewpoint, dtype=np.float64).reshape(3))
+        L.check(L.lib().pcr_normals_radius(ctx.handle, cloud.handle, float(radius), L.dptr(vp), L.dptr(out), L.iptr(counts) if return_counts else None), ctx.handle)
+    finally:
+        if own is not None:
+            own.free()
+    return (out, counts) if return_counts else out
+
+
 def compute_fpfh_feature(points, normals=None, radius=10.0, max_nn=100, ctx=None):
     """o3d.pipelines.registration.compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) (main.py:44-46).
     ``points`` may carry ``.normals``; returns a Feature with ``.data`` (33, N)."""
@@ -347,7 +364,7 @@ def execute_global_registration(source_down, target_down, source_fpfh, target_fp
 
 
 def ransac_init(src_cloud, tgt_cloud, voxel_size=2.0, seed=0, ctx=None, detector="voxel", iss_radius=None, iss_count=400,
-                return_info=False):
+                return_info=False, harris_radius=None, harris_threshold=0.001):
     """icp_template.py:56-110 -> (R (3,3), t (3,1)): feature DETECTION, feature DESCRIPTION (FPFH, 33-d),
     correspondence = mutual nearest features, then RANSAC with procrustes_transformation on 3 samples.
 
@@ -356,27 +373,40 @@ def ransac_init(src_cloud, tgt_cloud, voxel_size=2.0, seed=0, ctx=None, detector
                       (Keypoint_detection_ISS/ISS.py:35-73 on the GPU, pcr_iss) of the down-sampled cloud, at most
                       iss_count + 1 per cloud; descriptors are computed on the whole down-sampled cloud (their support) and
                       only the keypoints' rows are matched and sampled by RANSAC.
+    detector="harris": the same plan with the reference's PCLKeypoint.keypointHarris3D (is_nms=True) as the detector: radius
+                      harris_radius (default 2.5 voxels, like iss_radius), threshold harris_threshold.
     """
     s_down, s_f = preprocess_point_cloud(src_cloud, voxel_size, ctx=ctx)
     t_down, t_f = preprocess_point_cloud(tgt_cloud, voxel_size, ctx=ctx)
     info = {"detector": detector, "n_src": len(s_down.points), "n_tgt": len(t_down.points)}
-    if detector == "iss":
-        from .iss import iss_keypoints
+    if detector in ("iss", "harris"):
+        if detector == "iss":
+            from .iss import iss_keypoints
 
-        r = float(iss_radius) if iss_radius else 2.5 * voxel_size
-        ks = np.asarray(iss_keypoints(s_down.points, radius=r, non_max_radius=r, iss_count=iss_count, ctx=ctx), dtype=np.int64)
-        kt = np.asarray(iss_keypoints(t_down.points, radius=r, non_max_radius=r, iss_count=iss_count, ctx=ctx), dtype=np.int64)
-        info.update(n_src_keypoints=len(ks), n_tgt_keypoints=len(kt), iss_radius=r)
-        if len(ks) < 3 or len(kt) < 3:
-            raise ValueError(f"ISS found {len(ks)} / {len(kt)} keypoints: need at least 3 per cloud (lower the eigenvalue-ratio "
-                             "thresholds, change iss_radius, or use detector='voxel')")
+            r = float(iss_radius) if iss_radius else 2.5 * voxel_size
+            ks = np.asarray(iss_keypoints(s_down.points, radius=r, non_max_radius=r, iss_count=iss_count, ctx=ctx), dtype=np.int64)
+            kt = np.asarray(iss_keypoints(t_down.points, radius=r, non_max_radius=r, iss_count=iss_count, ctx=ctx), dtype=np.int64)
+            info.update(n_src_keypoints=len(ks), n_tgt_keypoints=len(kt), iss_radius=r)
+            if len(ks) < 3 or len(kt) < 3:
+                raise ValueError(f"ISS found {len(ks)} / {len(kt)} keypoints: need at least 3 per cloud (lower the eigenvalue-ratio "
+                                 "thresholds, change iss_radius, or use detector='voxel')")
+        else:
+            from .PCLKeypoint import keypointHarris3D
+
+            r = float(harris_radius) if harris_radius else 2.5 * voxel_size
+            ks = keypointHarris3D(s_down.points, radius=r, nms_threshold=harris_threshold, is_nms=True, return_indices=True, ctx=ctx)[1]
+            kt = keypointHarris3D(t_down.points, radius=r, nms_threshold=harris_threshold, is_nms=True, return_indices=True, ctx=ctx)[1]
+            info.update(n_src_keypoints=len(ks), n_tgt_keypoints=len(kt), harris_radius=r)
+            if len(ks) < 3 or len(kt) < 3:
+                raise ValueError(f"Harris-3D found {len(ks)} / {len(kt)} keypoints: need at least 3 per cloud (lower harris_threshold, change "
+                                 "harris_radius, or use detector='voxel')")
         s_kp, t_kp = PointCloud(np.asarray(s_down.points)[ks]), PointCloud(np.asarray(t_down.points)[kt])
         s_kf, t_kf = Feature(np.asarray(s_f.data)[:, ks]), Feature(np.asarray(t_f.data)[:, kt])
         res = execute_global_registration(s_kp, t_kp, s_kf, t_kf, voxel_size, seed=seed, ctx=ctx)
     elif detector == "voxel":
         res = execute_global_registration(s_down, t_down, s_f, t_f, voxel_size, seed=seed, ctx=ctx)
     else:
-        raise ValueError("detector must be 'voxel' or 'iss'")
+        raise ValueError("detector must be 'voxel', 'iss' or 'harris'")
     T = res.transformation
     R, t = T[:3, :3].copy(), T[:3, 3].reshape(3, 1).copy()
     if return_info:
