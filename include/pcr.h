@@ -1014,6 +1014,100 @@ PCR_API int pcr_objects_kitti_boxes(pcr_ctx* ctx, const pcr_objects* objs, const
 PCR_API int pcr_objects_match_labels(pcr_ctx* ctx, const pcr_objects* objs, const pcr_kitti_calib* calib, const double* labels /* L*16, host */, int64_t L,
                                      double* result /* L*8, host */, uint64_t* sel_bits /* L*words, host, or NULL */, int64_t words);
 
+/* -------------------------------------------------------------- KITTI evaluation
+ * What the reference runs on the label files it has written (Final_Project/README.md:225-236: `evaluate_object_3d_offline` of the
+ * kitti_eval submodule, which the reference carries only as an empty directory): box overlaps, the greedy detection-to-label matching
+ * and the average precision per class, metric and difficulty.  The tool's source is not part of the reference, so THIS COMMENT IS THE
+ * DEFINITION; parity with the tool's own binary is UNPINNED.  tests/kitti_eval_checks.py restates the rules in NumPy.
+ *
+ * Rows.  A box is 16 doubles in the order of the label file (detection.KITTI_COLUMNS): 0 type, 1 truncated, 2 occluded, 3 alpha,
+ *   4..7 left, top, right, bottom, 8..10 height, width, length, 11..13 cx, cy, cz, 14 ry, 15 score.  `type` is a code: 0 Car,
+ *   1 Pedestrian, 2 Cyclist, 3 Van, 4 Person_sitting, 5 DontCare, 6 anything else.  Frames are ragged: frame f owns the detections
+ *   det_first[f] .. det_first[f+1] and the labels gt_first[f] .. gt_first[f+1] (first[0] = 0, ascending).  A frame holds at most
+ *   PCR_KITTI_EVAL_MAX_DET detections and PCR_KITTI_EVAL_MAX_GT labels: otherwise PCR_E_UNSUPPORTED, and nothing is written.
+ *   Everything is binary64; cos(ry) and sin(ry) are taken on the host (no transcendental runs on the device).
+ *
+ * Overlap of a first box a (the detection) and a second box b, criterion c = -1 union, 0 the first box, 1 the second:
+ *   ratio(i, A, B) = i / ((A + B) - i) for c = -1,  i / A for c = 0,  i / B for c = 1.
+ *   image (metric 0):  w = min(right_a, right_b) - max(left_a, left_b),  h = min(bottom_a, bottom_b) - max(top_a, top_b), no +1;
+ *     w <= 0 or h <= 0: 0;  otherwise ratio(w*h, (right_a-left_a)*(bottom_a-top_a), (right_b-left_b)*(bottom_b-top_b)).
+ *   ground (metric 1): a box is the rectangle with local corners k = 0..3 (x, z) = (+l/2, +w/2), (-l/2, +w/2), (-l/2, -w/2),
+ *     (+l/2, -w/2), mapped by X = (cos*x + sin*z) + ox, Z = (cos*z - sin*x) + oz; BOTH quads relative to the centre of a: for a
+ *     (ox, oz) = (0, 0), for b (cx_b - cx_a, cz_b - cz_a) (absolute coordinates of some 50 m would cancel into areas of a few m^2).
+ *     b's quad is clipped in turn by the lines through a's corners 0->1, 1->2, 2->3, 3->0.  With e = Q - P the side of a vertex is
+ *     s = e_x*(Z - P_z) - e_z*(X - P_x), s >= 0 is inside (a vertex on the line is inside); the output takes, for every vertex V_i in
+ *     order, V_i if inside and then, if V_i and its successor V_j differ in side, V_i + t*(V_j - V_i) with t = s_i/(s_i - s_j).
+ *     area = 0.5 * sum over the vertices in order, from +0.0, of (X_i*Z_j - X_j*Z_i); fewer than 3 vertices or area <= 0: 0.
+ *     ratio(area, l_a*w_a, l_b*w_b).  A box with l <= 0 or w <= 0 overlaps nothing.
+ *   3-D (metric 2): hh = min(cy_a, cy_b) - max(cy_a - h_a, cy_b - h_b); hh <= 0 or a box with h <= 0: 0; otherwise
+ *     ratio(area*hh, (h_a*l_a)*w_a, (h_b*l_b)*w_b).
+ *   A field that is not finite among those a metric reads (image 4..7; ground 9, 10, 11, 13, 14; 3-D also 8, 12) makes it 0.
+ *   pcr_kitti_box_overlap is this on the host for one pair (cos, sin from the C library); the kernel compiles the same source.
+ *
+ * Constants.  min_overlap[metric][class]: 0.7 / 0.5 / 0.5 for Car / Pedestrian / Cyclist in every metric by default (finite and
+ *   >= 0, else PCR_E_INVALID).  Difficulty easy / moderate / hard: MIN_HEIGHT 40 / 25 / 25 on height2d = bottom - top,
+ *   MAX_OCCLUSION 0 / 1 / 2, MAX_TRUNCATION 0.15 / 0.30 / 0.50.  PCR_KITTI_EVAL_SAMPLES = 41 recall sample points.
+ *
+ * Cleaning, per (class, difficulty).  A label of the class is IGNORED (flag 1) if occluded > MAX_OCCLUSION or truncated >
+ *   MAX_TRUNCATION or height2d < MIN_HEIGHT, else COUNTED (flag 0; n_gt counts these).  A label of the neighbouring class (Van for
+ *   Car, Person_sitting for Pedestrian) has flag 1.  DontCare rows form the frame's don't-care list.  Every other label is absent
+ *   (flag -1).  A detection of the class has flag 1 if height2d < MIN_HEIGHT, else 0; other detections -1.
+ *
+ * Matching (the tool's computeStatistics), per frame, for a threshold t; mode 1 collects scores (t is not used), mode 2 counts.
+ *   Labels in row order, skipping flag -1 and don't-care rows.  Per label, the detections in row order, skipping flag -1, assigned
+ *   ones and, in mode 2, those with score < t; o = the metric's overlap (detection, label), c = -1; only o > min_overlap takes part.
+ *     mode 1: the first such detection is the candidate; a later one replaces it only with a strictly greater score.
+ *     mode 2: a flag-0 detection becomes the candidate if o > best (best starts at 0 and becomes o) or if the candidate has flag 1;
+ *             a flag-1 detection becomes the candidate only while there is none (best stays).
+ *   No candidate: fn += 1 if the label has flag 0.  A candidate is marked assigned; if neither it nor the label has flag 1,
+ *   tp += 1, and mode 1 emits the candidate's score.
+ *   Mode 2, after the labels: fp += 1 per detection that is unassigned, has flag 0 and score >= t.  Then for every don't-care row
+ *   (outer loop, row order) and every such detection (inner loop): if the metric's overlap with c = 0 exceeds min_overlap, the
+ *   detection is marked assigned and fp -= 1.  (KITTI's don't-care rows carry -1 / -1000 in their 3-D fields: they overlap nothing
+ *   in the ground and 3-D metrics, by the rules above.)
+ *
+ * Thresholds and AP, per (class, metric, difficulty): v = the mode-1 scores of all frames, descending; current = 0; for i = 0 ..
+ *   len-1: l = (i+1)/n_gt, r = (i+2)/n_gt if i < len-1 else l; if (r - current) < (current - l) and i < len-1, skip; otherwise
+ *   emit v[i] and current += 1.0/40.0.  At most 41 are emitted.  For threshold k, with the mode-2 counts summed over the frames:
+ *   recall[k] = tp/(double)(tp+fn), precision[k] = tp/(double)(tp+fp), 0 with a zero denominator; entries past n_thresholds are 0;
+ *   then precision[k] = max(precision[k..40]).  ap11 = 100*(S/11.0), S = precision[0] + precision[4] + ... + precision[40] added in
+ *   that order from +0.0; ap40 = 100*(S/40.0) over precision[1..40].  Orientation similarity is out of scope.
+ *
+ * The calls.  det / gt: host arrays of D x 16 and G x 16 doubles (NULL allowed when empty); det_first, gt_first: F + 1 entries.
+ *   pcr_kitti_eval_overlaps: the three matrices for `criterion`, ragged: frame f's nd x ng block, detection-major, starts at
+ *     pair_first[f]; any output may be NULL (each matrix holds pair_first[F] doubles, pair_first_out F + 1 entries).
+ *   pcr_kitti_eval_match: one (cls, difficulty, metric) through the kernels of the whole evaluation.  mode 1: scores_out (capacity:
+ *     the number of labels of the class) gets the emitted scores of all frames, descending, *n_scores_out their number, tp_out[0] /
+ *     fn_out[0] the sums and fp_out[0] n_gt, the labels with flag 0 (one that takes a flag-1 detection is neither tp nor fn).  mode 2: tp_out, fp_out, fn_out [n_thresholds <= 41] for the given thresholds.  Outputs not named for a
+ *     mode may be NULL and are left alone.
+ *   pcr_kitti_eval: everything; result->cell[class][metric][difficulty].  stage_ms (3 doubles, or NULL): device time of the overlap
+ *     pass, of mode 1 with the sort and the threshold pick, and of mode 2, by HIP events.  Thresholds are picked on the device; the
+ *     only read-back is the final one.  The result depends on neither the order of the frames nor on the run.
+ * PCR_E_INVALID: a NULL context, params or result; F < 0; first arrays NULL, not starting at 0 or descending; rows NULL while
+ *   counted; cls, difficulty or metric outside 0..2; mode other than 1, 2; n_thresholds outside 0..41; criterion outside -1..1.    */
+#define PCR_KITTI_EVAL_MAX_DET 256
+#define PCR_KITTI_EVAL_MAX_GT 128
+#define PCR_KITTI_EVAL_SAMPLES 41
+#define PCR_KITTI_ROW_DOUBLES 16
+typedef struct pcr_kitti_eval_params { double min_overlap[3][3]; /* [metric][class] */ double reserved[7]; } pcr_kitti_eval_params;
+typedef struct pcr_kitti_eval_cell {
+    int64_t n_gt, n_thresholds;
+    double thresholds[PCR_KITTI_EVAL_SAMPLES];
+    int64_t tp[PCR_KITTI_EVAL_SAMPLES], fp[PCR_KITTI_EVAL_SAMPLES], fn[PCR_KITTI_EVAL_SAMPLES];
+    double precision[PCR_KITTI_EVAL_SAMPLES], recall[PCR_KITTI_EVAL_SAMPLES];
+    double ap11, ap40;
+} pcr_kitti_eval_cell;
+typedef struct pcr_kitti_eval_result { pcr_kitti_eval_cell cell[3][3][3]; /* [class][metric][difficulty] */ } pcr_kitti_eval_result;
+PCR_API void pcr_kitti_eval_default_params(pcr_kitti_eval_params* params);
+PCR_API int pcr_kitti_box_overlap(const double a[16], const double b[16], int metric, int criterion, double* out);
+PCR_API int pcr_kitti_eval_overlaps(pcr_ctx* ctx, const double* det, const int64_t* det_first, const double* gt, const int64_t* gt_first, int64_t F,
+                                    int criterion, double* image_out, double* ground_out, double* volume_out, int64_t* pair_first_out);
+PCR_API int pcr_kitti_eval_match(pcr_ctx* ctx, const double* det, const int64_t* det_first, const double* gt, const int64_t* gt_first, int64_t F,
+                                 const pcr_kitti_eval_params* params, int cls, int difficulty, int metric, const double* thresholds, int n_thresholds,
+                                 int mode, int64_t* tp_out, int64_t* fp_out, int64_t* fn_out, double* scores_out, int64_t* n_scores_out);
+PCR_API int pcr_kitti_eval(pcr_ctx* ctx, const double* det, const int64_t* det_first, const double* gt, const int64_t* gt_first, int64_t F,
+                           const pcr_kitti_eval_params* params, pcr_kitti_eval_result* result, double* stage_ms);
+
 /* ------------------------------------------------------------- timing aid
  * HIP-event stopwatch on the ctx stream, for bench.py's roofline figures.   */
 PCR_API int pcr_timer_start(pcr_ctx* ctx);

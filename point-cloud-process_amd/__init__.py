@@ -84,6 +84,8 @@ from .extract import (  # noqa: F401
     transform_from_cam_to_velo,
     transform_from_velo_to_obj,
 )
+from . import kitti_eval  # noqa: F401
+from .kitti_eval import box_overlaps, evaluate_object_3d_offline, frames_from, read_label_dir, read_label_file  # noqa: F401
 from .gmm import GMM  # noqa: F401
 from .kmeans import K_Means  # noqa: F401
 from .spectral import knn_graph, spectral_clustering, spetral_clustering  # noqa: F401

@@ -42,6 +42,10 @@ PCR_KITTI_BOX_DOUBLES = 16
 PCR_KITTI_LDS_ROWS = 512
 PCR_LABEL_DOUBLES = 16
 PCR_LABEL_RESULT_DOUBLES = 8
+PCR_KITTI_EVAL_MAX_DET = 256
+PCR_KITTI_EVAL_MAX_GT = 128
+PCR_KITTI_EVAL_SAMPLES = 41
+PCR_KITTI_ROW_DOUBLES = 16
 
 
 class IcpParams(C.Structure):
@@ -188,6 +192,29 @@ class KittiCalib(C.Structure):
         ("P2", C.c_double * 12),
         ("reserved", C.c_double * 4),
     ]
+
+
+class KittiEvalParams(C.Structure):
+    _fields_ = [("min_overlap", (C.c_double * 3) * 3), ("reserved", C.c_double * 7)]   # [metric][class]
+
+
+class KittiEvalCell(C.Structure):
+    _fields_ = [
+        ("n_gt", C.c_int64),
+        ("n_thresholds", C.c_int64),
+        ("thresholds", C.c_double * PCR_KITTI_EVAL_SAMPLES),
+        ("tp", C.c_int64 * PCR_KITTI_EVAL_SAMPLES),
+        ("fp", C.c_int64 * PCR_KITTI_EVAL_SAMPLES),
+        ("fn", C.c_int64 * PCR_KITTI_EVAL_SAMPLES),
+        ("precision", C.c_double * PCR_KITTI_EVAL_SAMPLES),
+        ("recall", C.c_double * PCR_KITTI_EVAL_SAMPLES),
+        ("ap11", C.c_double),
+        ("ap40", C.c_double),
+    ]
+
+
+class KittiEvalResult(C.Structure):
+    _fields_ = [("cell", ((KittiEvalCell * 3) * 3) * 3)]   # [class][metric][difficulty]
 
 
 class GmmParams(C.Structure):
@@ -409,6 +436,13 @@ SIGNATURES = {
     "pcr_objects_kitti_boxes": (C.c_int, [_vp, _vp, C.POINTER(KittiCalib), C.POINTER(C.c_uint8), _dp]),
     # label match: (ctx, objects handle, calibration, L x 16 label doubles, L, L x 8 result doubles, L x words ballot words or NULL, words)
     "pcr_objects_match_labels": (C.c_int, [_vp, _vp, C.POINTER(KittiCalib), _dp, C.c_int64, _dp, C.POINTER(C.c_uint64), C.c_int64]),
+    # KITTI evaluation: (ctx, det rows, det_first, gt rows, gt_first, F, ...); the overlap of one pair on the host
+    "pcr_kitti_eval_default_params": (None, [C.POINTER(KittiEvalParams)]),
+    "pcr_kitti_box_overlap": (C.c_int, [_dp, _dp, C.c_int, C.c_int, _dp]),
+    "pcr_kitti_eval_overlaps": (C.c_int, [_vp, _dp, _lp, _dp, _lp, C.c_int64, C.c_int, _dp, _dp, _dp, _lp]),
+    "pcr_kitti_eval_match": (C.c_int, [_vp, _dp, _lp, _dp, _lp, C.c_int64, C.POINTER(KittiEvalParams), C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                       _lp, _lp, _lp, _dp, _lp]),
+    "pcr_kitti_eval": (C.c_int, [_vp, _dp, _lp, _dp, _lp, C.c_int64, C.POINTER(KittiEvalParams), C.POINTER(KittiEvalResult), _dp]),
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),
