@@ -99,6 +99,13 @@ static_assert(WT_PR % 64 == 0, "whole chunks");
 constexpr int WT_PASSES = 3, WT_PASSES_SEEDED = 1;   // passes of an unseeded / a seeded tile
 constexpr int WT_HEAVY_STOP = 384;  // (192: 78.8-81.2, 384: 77.6-79.0, 576: 79.8-80.0 us for a one-iteration registration of the 120k pair; without: 81.4-82.0)
 constexpr int WT_ROUNDS_SMALL = 768 / WT_PR, WT_ROUNDS_LARGE = 2304 / WT_PR;   // staged-point caps of 768 / 2304 per tile
+// Seeded passes of a launch with the small cap stop at 576: on Hilbert tiles the ~20 tiles that stage 577-768 points are the slowest
+// of a pass (16 us median against 13.5 for 385-576), and their 32 seeded queries each are served by the queue well before the tail
+// (bench.py, us per step: 32.28-32.75 against 33.43-34.26 with 768; 384: 38.4-38.9 -- DESIGN section 7).  The unseeded first pass keeps
+// 768: what it leaves open carries no candidate and costs the queue twice as much per item.  So does the two-launch pass: there the
+// queue is a launch of its own behind the tiles, and four pairs in flight lost 5 % with the lower cap (concurrent_pairs 5.86 against
+// 6.16-6.18e9).
+constexpr int WT_ROUNDS_SEEDED = 576 / WT_PR;
 
 struct wtile_lds {
     alignas(16) float px[WT_PR + 8], py[WT_PR + 8], pz[WT_PR + 8];
@@ -2263,7 +2270,10 @@ int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const p
                 pa.pass_id = (unsigned int)(enq + c);
                 pa.notify = c == chunk - 1 ? 1u : 0u;
                 // (the busy cap only where the drain launch exists and logs its item counts: two-launch passes)
-                const unsigned int cap_n = wtile_point_cap(ctx, nq), cap_busy = (!inline_queue && cap_n > (unsigned int)(WT_PR * WT_ROUNDS_SMALL)) ? WT_BUSY_CAP : cap_n;
+                // (a seeded one-launch pass under the small cap stages 576 points at most, see WT_ROUNDS_SEEDED)
+                const unsigned int cap_launch = wtile_point_cap(ctx, nq);
+                const unsigned int cap_n = (use_prev && inline_queue && cap_launch == (unsigned int)(WT_PR * WT_ROUNDS_SMALL)) ? (unsigned int)(WT_PR * WT_ROUNDS_SEEDED) : cap_launch;
+                const unsigned int cap_busy = (!inline_queue && cap_launch > (unsigned int)(WT_PR * WT_ROUNDS_SMALL)) ? WT_BUSY_CAP : cap_n;
                 hipLaunchKernelGGL(grid_pass_kernel, dim3(wtile_blocks(nq)), dim3(256), 0, ctx->stream, (const pcr_grid_view*)idx->d_view, idx->view, qc->d, (long long)nq,
                                    params->max_d2, WT_XCD_REMAP, cap_n, cap_busy, sc.res_pos.as<unsigned int>(), ctx->d_debug, use_prev ? 1 : 0, inline_queue, pa);
                 if (ctx->profile) pcr_prof_mark(ctx, 1);

@@ -82,12 +82,28 @@ blk_rt = (w[:, 2] - w[:, 0]).reshape(nblk, 4).max(axis=1).astype(np.float64)
 ok = (blk_cyc > 0) & (blk_rt > 0)
 cyc_per_us = float(np.median(blk_cyc[ok] / blk_rt[ok])) * 100.0 if ok.any() else 0.0
 item_end = []
+rows = []   # items of THIS pass: start, duration (us on the serving wave's clock), with candidate, descent steps, points scanned
 full = buf[(1 << 17):(1 << 17) + 240000].reshape(-1, 4)
 for g in range(32):
     for k in range(int(it_g[g])):
         e = full[g + 32 * k]
         if g + 32 * k < 59999 and e[0] > 0 and cyc_per_us > 0:
             item_end.append((float(int(e[1]) & 0xffffffff) * 16.0 + float(e[0])) / cyc_per_us)
+            rows.append((float(int(e[1]) & 0xffffffff) * 16.0 / cyc_per_us, float(e[0]) / cyc_per_us, int(e[3]) & 1, int(e[1]) >> 32, int(e[2]) & 0xffffffff))
+if rows:
+    # ("hard items" above counts every record in the block, the unseeded first pass's included: these are the last pass's alone)
+    rw = np.array(rows)
+    print("items of this pass by start (us after the serving wave's start): count, with a candidate, duration median / max, points scanned median, last end")
+    for lo, hi in [(0, 8), (8, 12), (12, 15), (15, 18), (18, 99)]:
+        m = (rw[:, 0] >= lo) & (rw[:, 0] < hi)
+        if m.any():
+            print("   %2d-%2d: %5d items, %5d with a candidate, duration %.2f / %.2f us, points %d, last end %.2f" % (lo, hi, m.sum(), rw[m, 2].sum(), np.median(rw[m, 1]), rw[m, 1].max(), np.median(rw[m, 4]), (rw[m, 0] + rw[m, 1]).max()))
+    for c, nm in ((1, "with a candidate"), (0, "without one")):
+        m = rw[:, 2] == c
+        if m.any():
+            print("   %-17s %5d items, duration pct 50/90/99/max" % (nm, m.sum()), pc(rw[m, 1]).round(2), "us, descent steps median %d, points median %d" % (np.median(rw[m, 3]), np.median(rw[m, 4])))
+    o = np.argsort(-(rw[:, 0] + rw[:, 1]))[:8]
+    print("   the last to end (start, duration, candidate, steps, points):", [(round(float(rw[i, 0]), 1), round(float(rw[i, 1]), 1), int(rw[i, 2]), int(rw[i, 3]), int(rw[i, 4])) for i in o])
 start_med = float(np.median(us(w[:, 0])))
 # (the wave that writes the poison takes its "moments in" stamp behind those stores: a tile's span is capped at the 99th percentile)
 span = w[:, 2] - w[:, 1]
