@@ -368,6 +368,17 @@ PCR_API int pcr_normals(pcr_ctx* ctx, const pcr_cloud* cloud, int k, double* nor
  *   toward viewpoint[3] (NULL = origin); orient == 0 leaves the solver's sign.
  * pcr_fpfh: compute_fpfh_feature (main.py:44-46); normals (n,3) by row;
  *   features_out (n,33) row-major (= Open3D's Feature.data (33,n) column-major).
+ * pcr_fpfh_rows: the descriptors of m chosen rows (keypoints described over the
+ *   cloud as search surface).  features_out[i] (m,33) holds, bit for bit, row
+ *   rows[i] of what pcr_fpfh writes for the same cloud, normals, radius and
+ *   max_nn; rows may be in any order and may repeat.  Only the SPFH of the rows
+ *   that the chosen rows' neighbour lists reach is computed: *n_spfh_out (may be
+ *   NULL) receives how many distinct rows that were -- the size of the union of
+ *   the lists, each of which holds its own row (a row with max_nn or more exact
+ *   duplicates of lower row number in front of it is counted besides its list).
+ *   NULL arguments, m < 0 or a row outside [0, n): PCR_E_INVALID before anything
+ *   is launched or allocated; m == 0: PCR_OK, nothing written, *n_spfh_out = 0;
+ *   every other status as pcr_fpfh reports it.
  * pcr_feature_match: nearest target row in feature space for every query row
  *   (find_matchings, icp_template.py:20-41); squared L2, ties to the lowest row.
  * pcr_ransac: registration_ransac_based_on_feature_matching's loop
@@ -393,6 +404,9 @@ typedef struct pcr_ransac_result {
 PCR_API int pcr_normals_hybrid(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int max_nn, int orient, const double viewpoint[3],
                                double* normals_out);
 PCR_API int pcr_fpfh(pcr_ctx* ctx, const pcr_cloud* cloud, const double* normals, double radius, int max_nn, double* features_out);
+PCR_API int pcr_fpfh_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const double* normals /* (n,3) by caller row, host */, double radius, int max_nn,
+                          const int64_t* rows /* m caller rows, host */, int64_t m, double* features_out /* (m,33) row-major, host */,
+                          int64_t* n_spfh_out /* may be NULL */);
 PCR_API int pcr_feature_match(pcr_ctx* ctx, const double* queries, int64_t nq, const double* targets, int64_t nt, int dim,
                               int32_t* idx_out, double* d2_out);
 PCR_API int pcr_ransac_default_params(pcr_ransac_params* p);

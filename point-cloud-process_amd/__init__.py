@@ -41,6 +41,7 @@ from .pca_normal import PCA, estimate_normals  # noqa: F401
 from .global_registration import (  # noqa: F401
     Feature,
     RegistrationResult,
+    compute_fpfh_at_rows,
     compute_fpfh_feature,
     estimate_normals_hybrid,
     estimate_normals_radius,

@@ -375,6 +375,7 @@ SIGNATURES = {
     "pcr_normals": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _ip]),
     "pcr_normals_hybrid": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_int, _dp, _dp]),
     "pcr_fpfh": (C.c_int, [_vp, _vp, _dp, C.c_double, C.c_int, _dp]),
+    "pcr_fpfh_rows": (C.c_int, [_vp, _vp, _dp, C.c_double, C.c_int, _lp, C.c_int64, _dp, _lp]),
     "pcr_feature_match": (C.c_int, [_vp, _dp, C.c_int64, _dp, C.c_int64, C.c_int, _ip, _dp]),
     "pcr_ransac_default_params": (C.c_int, [C.POINTER(RansacParams)]),
     "pcr_ransac": (C.c_int, [_vp, _vp, _vp, _ip, C.c_int64, C.POINTER(RansacParams), C.POINTER(RansacResult)]),

@@ -1,6 +1,7 @@
 // Descriptors of the global initialisation in front of ICP -- the Open3D calls of Registration/main.py:33-47:
 //   pcr_normals_hybrid   estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))      main.py:39-40
 //   pcr_fpfh             compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) main.py:44-46
+//   pcr_fpfh_rows        the same descriptors at chosen rows only (keypoints over the cloud as search surface), bit for bit
 // Open3D is a third-party dependency that is absent here and unpinned in the reference: the algorithms below
 // follow its published behaviour (FPFH of Rusu et al. 2009 as implemented by Open3D >= 0.12: 3 x 11 bins,
 // increments 100/(k-1), neighbour SPFH weighted by 1/d^2 and renormalised to 100 per sub-histogram).
@@ -13,6 +14,7 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
+#include <rocprim/rocprim.hpp>
 #include "pcr_grid_dev.h"
 #include "pcr_linalg.h"
 #include "pcr_global_dev.h"
@@ -294,22 +296,30 @@ __device__ static inline int clamp_bin(double x) {
     return h < 0 ? 0 : (h > 10 ? 10 : h);
 }
 
-template <int CAP>
-__device__ static bool spfh_body(const pcr_grid_view& gv, const pcr_pt& p, double r2, int max_nn, const double* __restrict__ normals /* by row */,
-                                 double* __restrict__ spfh /* (n,33) by row */, unsigned int* __restrict__ nb_id /* (n,max_nn) by row */, double* __restrict__ nb_d2,
-                                 int* __restrict__ nb_cnt, int* __restrict__ fail, hybrid_lds_t<CAP>* L, int* hist /* LDS, 33 */) {
+// Where ONE row's results go.  The full pass keeps every row's list for fpfh_kernel (LISTS); the rows pass (below) keeps only its
+// SPFH, in a compact block.  The destination and the list store are the only differences: the pair loop, the binning, the skip of
+// list entry 0 and the repeated-addition scaling exist once.
+struct spfh_dest {
+    double* __restrict__ spfh;                                                               // 33
+    unsigned int* __restrict__ nb_id; double* __restrict__ nb_d2; int* __restrict__ nb_cnt;    // (max_nn) twice, one count; unused without LISTS
+};
+__device__ static inline spfh_dest spfh_dest_by_row(long long row, int max_nn, double* spfh, unsigned int* nb_id, double* nb_d2, int* nb_cnt) {
+    return spfh_dest{spfh + 33 * row, nb_id + row * max_nn, nb_d2 + row * max_nn, nb_cnt + row};
+}
+template <int CAP, bool LISTS>
+__device__ static bool spfh_body(const pcr_grid_view& gv, const pcr_pt& p, double r2, int max_nn, const double* __restrict__ normals /* by row */, const spfh_dest& out,
+                                 int* __restrict__ fail, hybrid_lds_t<CAP>* L, int* hist /* LDS, 33 */) {
     nb_entry* const nb = L->nb;
     if (threadIdx.x < 33) hist[threadIdx.x] = 0;
     const int cnt = gather_hybrid<CAP>(gv, p.x, p.y, p.z, r2, max_nn, L);  // ends with a barrier
     if (cnt == -2) return false;
     // (an empty list: the FPFH launch behind this one reads every point's count -- and walks that many entries -- before the host sees the fail word)
-    if (cnt < 0) { if (threadIdx.x == 0) { atomicAdd(fail, 1); nb_cnt[p.id] = 0; } return true; }
+    if (cnt < 0) { if (threadIdx.x == 0) { atomicAdd(fail, 1); if (LISTS) *out.nb_cnt = 0; } return true; }
     const double p1[3] = {p.x, p.y, p.z};
     const double n1[3] = {normals[3 * p.id], normals[3 * p.id + 1], normals[3 * p.id + 2]};
     for (int k = threadIdx.x; k < cnt; k += 64) {
         const nb_entry en = nb[k];
-        nb_id[(long long)p.id * max_nn + k] = en.id;
-        nb_d2[(long long)p.id * max_nn + k] = en.d2;
+        if (LISTS) { out.nb_id[k] = en.id; out.nb_d2[k] = en.d2; }
         if (k == 0) continue;  // the query point itself (or a duplicate of it)
         const pcr_pt b = gv.pts[en.pos];
         const double p2[3] = {b.x, b.y, b.z};
@@ -321,14 +331,14 @@ __device__ static bool spfh_body(const pcr_grid_view& gv, const pcr_pt& p, doubl
         atomicAdd(&hist[22 + clamp_bin(11.0 * (f[2] + 1.0) * 0.5)], 1);
     }
     __syncthreads();
-    if (threadIdx.x == 0) nb_cnt[p.id] = cnt;
+    if (LISTS && threadIdx.x == 0) *out.nb_cnt = cnt;
     if (threadIdx.x < 33) {
         double v = 0.0;
         if (cnt > 1) {
             const double incr = 100.0 / (double)(cnt - 1);
             for (int c = 0; c < hist[threadIdx.x]; ++c) v += incr;  // repeated addition, like the reference library
         }
-        spfh[33 * (long long)p.id + threadIdx.x] = v;
+        out.spfh[threadIdx.x] = v;
     }
     return true;
 }
@@ -341,7 +351,7 @@ spfh_kernel(pcr_grid_view gv, long long n, double r2, int max_nn, const double* 
     const long long i = blockIdx.x;
     if (i >= n) return;
     const pcr_pt p = gv.pts[i];
-    spfh_body<NB_CAP>(gv, p, r2, max_nn, normals, spfh, nb_id, nb_d2, nb_cnt, fail, &s_L, hist);
+    spfh_body<NB_CAP, true>(gv, p, r2, max_nn, normals, spfh_dest_by_row(p.id, max_nn, spfh, nb_id, nb_d2, nb_cnt), fail, &s_L, hist);
 }
 
 template <int CAP>
@@ -357,8 +367,8 @@ spfh_scans_kernel(scans_view V, long long ng, double r2, int max_nn, const doubl
         pcr_grid_view gv;
         const size_t base = scans_block_view(V, i, &gv);
         const pcr_pt p = V.down[i];
-        const bool done = spfh_body<CAP>(gv, p, r2, max_nn, normals + 3 * base, spfh + 33 * base, nb_id + base * (size_t)max_nn, nb_d2 + base * (size_t)max_nn, nb_cnt + base,
-                                         fail, &s_L, hist);
+        const bool done = spfh_body<CAP, true>(gv, p, r2, max_nn, normals + 3 * base,
+                                               spfh_dest_by_row(p.id, max_nn, spfh + 33 * base, nb_id + base * (size_t)max_nn, nb_d2 + base * (size_t)max_nn, nb_cnt + base), fail, &s_L, hist);
         if (!done && threadIdx.x == 0) redo[atomicAdd(redo_count, 1u)] = (unsigned int)i;
         __syncthreads();
     }
@@ -368,11 +378,20 @@ spfh_scans_kernel(scans_view V, long long ng, double r2, int max_nn, const doubl
 // One wave per point, lane = histogram bin (33 of 64).  The neighbour list (row, d^2) goes through LDS first, so the SPFH rows
 // of four neighbours are requested together instead of one dependent chain id -> row per neighbour; every term is spfh / d^2
 // (a true division, as in Open3D); the three renormalising sums are taken over the lanes of each 11-bin block at the end.
-__device__ static void fpfh_body(const long long i, int max_nn, const double* __restrict__ spfh, const unsigned int* __restrict__ nb_id, const double* __restrict__ nb_d2,
-                                 const int* __restrict__ nb_cnt, double* __restrict__ fpfh /* (n,33) by row */, unsigned int* s_id, double* s_d2, double* s_acc) {
+// `i`: the list (and the count) to walk; `self`: the SPFH row of the point itself; `fpfh`: its 33 outputs.  SLOT: the SPFH block is
+// compact and slot[row] says where a row's histogram sits (the rows pass below) -- the rows are translated on their way into LDS, the
+// sums behind that are the same instructions in the same order.
+template <bool SLOT>
+__device__ static void fpfh_body(const long long i, const long long self, int max_nn, const double* __restrict__ spfh, const unsigned int* __restrict__ slot,
+                                 const unsigned int* __restrict__ nb_id, const double* __restrict__ nb_d2, const int* __restrict__ nb_cnt, double* __restrict__ fpfh /* 33 */,
+                                 unsigned int* s_id, double* s_d2, double* s_acc) {
     const int cnt = nb_cnt[i];
     const int lane = threadIdx.x;
-    for (int k = lane; k < cnt; k += 64) { s_id[k] = nb_id[i * max_nn + k]; s_d2[k] = nb_d2[i * max_nn + k]; }
+    for (int k = lane; k < cnt; k += 64) {
+        const unsigned int id = nb_id[i * max_nn + k];
+        s_id[k] = SLOT ? slot[id] : id;
+        s_d2[k] = nb_d2[i * max_nn + k];
+    }
     __syncthreads();
     double acc = 0.0;
     if (cnt > 1 && lane < 33) {
@@ -399,9 +418,9 @@ __device__ static void fpfh_body(const long long i, int max_nn, const double* __
             double sum = 0.0;
 #pragma unroll
             for (int j = 0; j < 11; ++j) sum += s_acc[11 * g + j];
-            v = acc * (sum != 0.0 ? 100.0 / sum : 0.0) + spfh[33 * i + lane];
+            v = acc * (sum != 0.0 ? 100.0 / sum : 0.0) + spfh[33 * self + lane];
         }
-        fpfh[33 * i + lane] = v;
+        fpfh[lane] = v;
     }
 }
 
@@ -413,7 +432,7 @@ fpfh_kernel(long long n, int max_nn, const double* __restrict__ spfh, const unsi
     __shared__ double s_acc[33];
     const long long i = blockIdx.x;
     if (i >= n) return;
-    fpfh_body(i, max_nn, spfh, nb_id, nb_d2, nb_cnt, fpfh, s_id, s_d2, s_acc);
+    fpfh_body<false>(i, i, max_nn, spfh, nullptr, nb_id, nb_d2, nb_cnt, fpfh + 33 * i, s_id, s_d2, s_acc);
 }
 
 // (the records of a scan sit in row order: record base + r is row r)
@@ -427,7 +446,80 @@ fpfh_scans_kernel(scans_view V, long long ng, int max_nn, const double* __restri
     const long long i = blockIdx.x;
     if (i >= ng) return;
     const size_t base = V.scan_first[V.vsid[i]];
-    fpfh_body(i - (long long)base, max_nn, spfh + 33 * base, nb_id + base * (size_t)max_nn, nb_d2 + base * (size_t)max_nn, nb_cnt + base, fpfh + 33 * base, s_id, s_d2, s_acc);
+    const long long r = i - (long long)base;
+    fpfh_body<false>(r, r, max_nn, spfh + 33 * base, nullptr, nb_id + base * (size_t)max_nn, nb_d2 + base * (size_t)max_nn, nb_cnt + base, fpfh + 33 * (size_t)i, s_id, s_d2, s_acc);
+}
+
+// -------------------------------------------------------------- FPFH at chosen rows
+// The descriptor of a row needs its own list and SPFH and the SPFH of the rows in that list -- at most max_nn + 1 rows -- so m chosen
+// rows need at most m (max_nn + 1) histograms, not n.  Four launches and a compaction on the stream:
+//   fpfh_rows_lists_kernel   one wave per ENTRY of `rows` (any order, repeats allowed): its hybrid list -> an (m,max_nn) block, and the
+//                            word need[row] = 1 for every row of the list and for the entry's own row (plain stores of the same
+//                            constant: several waves may write one word, there is nothing to lose)
+//   rocprim::select          the marked rows, ascending, and their number M (it stays on the device; the launches behind it are sized by
+//                            the bound min(n, m (max_nn + 1)) that the host knows)
+//   spfh_rows_kernel         wave k < M: list and histogram of marked row k by spfh_body -> spfh[k]; need[row] becomes slot[row] = k
+//   fpfh_rows_kernel         fpfh_body over the m stored lists, SPFH rows found through slot[]
+// The same bits as the rows of the full pass, because nothing a row's result is made of depends on which other rows are computed:
+//   a list     is a function of the query's coordinates, the searched records, r^2, max_nn and the order (d^2, row) -- gather_hybrid
+//              on the same view (hybrid_space::open) whichever kernel calls it;
+//   an SPFH    is integer counts over that list, then count additions of one increment: spfh_body both times;
+//   an FPFH    adds spfh / d^2 in list order: fpfh_body both times.
+// The entry's own row is marked besides its list: with max_nn or more exact duplicates of lower row in front of it a row is not in its
+// own list, and fpfh_body still adds the row's own SPFH.  Without such duplicates M is the size of the union of the lists.
+// A record's position is not its row on a re-laid cloud or in a grid index's order: row_pos_kernel writes the table row -> position
+// for those (4 n bytes; a cloud searched without an index has its records in row order and needs none).
+__global__ void __launch_bounds__(256) row_pos_kernel(const pcr_pt* __restrict__ pts, long long n, unsigned int* __restrict__ row_pos) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) row_pos[pts[j].id] = (unsigned int)j;
+}
+
+__global__ void __launch_bounds__(64)
+fpfh_rows_lists_kernel(pcr_grid_view gv, long long n, const unsigned int* __restrict__ row_pos /* null: position = row */, double r2, int max_nn,
+                       const long long* __restrict__ rows, long long m, unsigned int* __restrict__ need /* (n), zeroed */, unsigned int* __restrict__ nb_id /* (m,max_nn) */,
+                       double* __restrict__ nb_d2, int* __restrict__ nb_cnt /* (m) */, int* __restrict__ fail) {
+    __shared__ hybrid_lds s_L;
+    const long long i = blockIdx.x;
+    if (i >= m) return;
+    const long long row = rows[i];
+    if (row < 0 || row >= n) { if (threadIdx.x == 0) nb_cnt[i] = 0; return; }   // (the entry point refuses such rows; a resident caller gets zeros)
+    const pcr_pt p = gv.pts[row_pos ? (long long)row_pos[row] : row];
+    const int cnt = gather_hybrid<NB_CAP>(gv, p.x, p.y, p.z, r2, max_nn, &s_L);
+    if (cnt < 0) { if (threadIdx.x == 0) { atomicAdd(fail, 1); nb_cnt[i] = 0; } return; }   // (as spfh_body: an empty list for the launch behind)
+    for (int k = threadIdx.x; k < cnt; k += 64) {
+        const nb_entry en = s_L.nb[k];
+        nb_id[i * max_nn + k] = en.id;
+        nb_d2[i * max_nn + k] = en.d2;
+        need[en.id] = 1u;
+    }
+    if (threadIdx.x == 0) { nb_cnt[i] = cnt; need[row] = 1u; }
+}
+
+__global__ void __launch_bounds__(64)
+spfh_rows_kernel(pcr_grid_view gv, const unsigned int* __restrict__ row_pos, double r2, int max_nn, const double* __restrict__ normals /* by row */,
+                 const unsigned int* __restrict__ marked, const unsigned int* __restrict__ n_marked, unsigned int* __restrict__ slot /* (n): was `need` */,
+                 double* __restrict__ spfh /* (bound,33) */, int* __restrict__ fail) {
+    __shared__ hybrid_lds s_L;
+    __shared__ int hist[33];
+    const unsigned int k = blockIdx.x;
+    if (k >= *n_marked) return;
+    const unsigned int row = marked[k];
+    if (threadIdx.x == 0) slot[row] = k;
+    const pcr_pt p = gv.pts[row_pos ? row_pos[row] : row];
+    spfh_body<NB_CAP, false>(gv, p, r2, max_nn, normals, spfh_dest{spfh + 33 * (size_t)k, nullptr, nullptr, nullptr}, fail, &s_L, hist);
+}
+
+__global__ void __launch_bounds__(64)
+fpfh_rows_kernel(long long n, long long m, int max_nn, const long long* __restrict__ rows, const double* __restrict__ spfh, const unsigned int* __restrict__ slot,
+                 const unsigned int* __restrict__ nb_id, const double* __restrict__ nb_d2, const int* __restrict__ nb_cnt, double* __restrict__ fpfh /* (m,33) */) {
+    __shared__ unsigned int s_id[NB_CAP];
+    __shared__ double s_d2[NB_CAP];
+    __shared__ double s_acc[33];
+    const long long i = blockIdx.x;
+    if (i >= m) return;
+    const long long row = rows[i];
+    if (row < 0 || row >= n) { if (threadIdx.x < 33) fpfh[33 * i + threadIdx.x] = 0.0; return; }
+    fpfh_body<true>(i, (long long)slot[row], max_nn, spfh, slot, nb_id, nb_d2, nb_cnt, fpfh + 33 * i, s_id, s_d2, s_acc);
 }
 
 // ------------------------------------------------------------------ host side
@@ -502,6 +594,40 @@ int pcr_fpfh_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_normal
     return launch_status(ctx);   // (the index and the scratch go back to the arena stream-ordered)
 }
 
+// Scratch: 12 m max_nn + 4 m for the lists, 4 n (8 n with the position table) for need / slot, 268 bytes per row of the bound for the
+// marked rows and their SPFH -- against n (12 max_nn + 268) of the full pass.
+int pcr_fpfh_rows_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_normals, double radius, int max_nn, const long long* d_rows, long long m, double* d_out,
+                         unsigned int* d_n_spfh) {
+    const long long n = cloud->n;
+    if (m <= 0) { PCR_HIP(ctx, hipMemsetAsync(d_n_spfh, 0, sizeof(unsigned int), ctx->stream)); return PCR_OK; }
+    const long long bound = m <= n / (max_nn + 1) ? m * (max_nn + 1) : n;   // >= the marked rows, whatever they turn out to be
+    pcr_dev_block need(ctx), rowpos(ctx), marked(ctx), spfh(ctx), nbid(ctx), nbd2(ctx), nbcnt(ctx), tmp(ctx);
+    int rc;
+    if (m > 0x7fffffffLL) return PCR_E_INVALID;   // (one block per entry)
+    if ((rc = need.alloc(sizeof(unsigned int) * n)) || (rc = marked.alloc(sizeof(unsigned int) * bound)) ||
+        (rc = spfh.alloc(sizeof(double) * 33 * bound)) || (rc = nbid.alloc(sizeof(unsigned int) * (size_t)max_nn * m)) || (rc = nbd2.alloc(sizeof(double) * (size_t)max_nn * m)) ||
+        (rc = nbcnt.alloc(sizeof(int) * m)))
+        return rc;
+    size_t tb = 0;
+    PCR_HIP(ctx, rocprim::select(nullptr, tb, rocprim::counting_iterator<unsigned int>(0u), need.as<unsigned int>(), marked.as<unsigned int>(), d_n_spfh, (size_t)n, ctx->stream));
+    if ((rc = tmp.alloc(tb > 0 ? tb : 16))) return rc;
+    hybrid_space sp(ctx);
+    if ((rc = sp.open(cloud, radius))) return rc;
+    const bool table = sp.idx != nullptr;   // (an index's records are in its own order; brute_view's are in row order)
+    if (table && (rc = rowpos.alloc(sizeof(unsigned int) * n))) return rc;
+    PCR_HIP(ctx, hipMemsetAsync(need.p, 0, sizeof(unsigned int) * n, ctx->stream));
+    if (table) hipLaunchKernelGGL(row_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, sp.view.pts, n, rowpos.as<unsigned int>());
+    const unsigned int* const pos = table ? rowpos.as<unsigned int>() : nullptr;
+    hipLaunchKernelGGL(fpfh_rows_lists_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, sp.view, n, pos, radius * radius, max_nn, d_rows, m, need.as<unsigned int>(),
+                       nbid.as<unsigned int>(), nbd2.as<double>(), nbcnt.as<int>(), fail_word(ctx));
+    PCR_HIP(ctx, rocprim::select(tmp.p, tb, rocprim::counting_iterator<unsigned int>(0u), need.as<unsigned int>(), marked.as<unsigned int>(), d_n_spfh, (size_t)n, ctx->stream));
+    hipLaunchKernelGGL(spfh_rows_kernel, dim3((unsigned)bound), dim3(64), 0, ctx->stream, sp.view, pos, radius * radius, max_nn, d_normals, (const unsigned int*)marked.as<unsigned int>(),
+                       (const unsigned int*)d_n_spfh, need.as<unsigned int>(), spfh.as<double>(), fail_word(ctx));
+    hipLaunchKernelGGL(fpfh_rows_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, n, m, max_nn, d_rows, (const double*)spfh.as<double>(), (const unsigned int*)need.as<unsigned int>(),
+                       (const unsigned int*)nbid.as<unsigned int>(), (const double*)nbd2.as<double>(), (const int*)nbcnt.as<int>(), d_out);
+    return launch_status(ctx);   // (the index and the scratch go back to the arena stream-ordered)
+}
+
 int pcr_scans_features(pcr_ctx* ctx, const scans_view& V, size_t ng, const pcr_global_params* g, const scans_scratch& w, double* d_fpfh) {
     unsigned int* const redo_n = pcr_counter(ctx, PCR_CW_FEATURES_REDO);   // [0]: normals, [1]: SPFH (zero between calls)
     const unsigned fixed = (unsigned)(ng < (size_t)(16 * ctx->cu_count) ? ng : (size_t)(16 * ctx->cu_count));
@@ -548,5 +674,29 @@ int pcr_fpfh(pcr_ctx* ctx, const pcr_cloud* cloud, const double* normals, double
     if ((rc = pcr_fpfh_device(ctx, cloud, nrm.as<double>(), radius, max_nn, out.as<double>()))) return rc;
     PCR_HIP(ctx, hipMemcpyAsync(features_out, out.p, sizeof(double) * 33 * n, hipMemcpyDeviceToHost, ctx->stream));
     return pcr_read_fail(ctx);
+}
+
+int pcr_fpfh_rows(pcr_ctx* ctx, const pcr_cloud* cloud, const double* normals, double radius, int max_nn, const int64_t* rows, int64_t m, double* features_out,
+                  int64_t* n_spfh_out) {
+    if (!ctx || !cloud || !normals || !rows || !features_out || m < 0 || !hybrid_params_ok(radius, max_nn, 2)) return PCR_E_INVALID;
+    if (cloud->n <= 0) return PCR_E_EMPTY;
+    const long long n = cloud->n;
+    for (int64_t i = 0; i < m; ++i)
+        if (rows[i] < 0 || rows[i] >= n) return PCR_E_INVALID;
+    if (m == 0) { if (n_spfh_out) *n_spfh_out = 0; return PCR_OK; }
+    static_assert(sizeof(long long) == sizeof(int64_t), "rows are uploaded as they are");
+    hipSetDevice(ctx->device);
+    pcr_dev_block nrm(ctx), d_rows(ctx), out(ctx), count(ctx);
+    int rc;
+    if ((rc = nrm.alloc(sizeof(double) * 3 * n)) || (rc = d_rows.alloc(sizeof(long long) * m)) || (rc = out.alloc(sizeof(double) * 33 * m)) || (rc = count.alloc(16))) return rc;
+    PCR_HIP(ctx, hipMemcpyAsync(nrm.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(d_rows.p, rows, sizeof(long long) * m, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = pcr_fpfh_rows_device(ctx, cloud, nrm.as<double>(), radius, max_nn, d_rows.as<long long>(), m, out.as<double>(), count.as<unsigned int>()))) return rc;
+    unsigned int n_spfh = 0;
+    PCR_HIP(ctx, hipMemcpyAsync(features_out, out.p, sizeof(double) * 33 * m, hipMemcpyDeviceToHost, ctx->stream));
+    PCR_HIP(ctx, hipMemcpyAsync(&n_spfh, count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = pcr_read_fail(ctx))) return rc;   // (the one wait of the call: both copies are done behind it)
+    if (n_spfh_out) *n_spfh_out = (int64_t)n_spfh;
+    return PCR_OK;
 }
 }  // extern "C"

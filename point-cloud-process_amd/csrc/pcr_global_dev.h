@@ -92,6 +92,10 @@ PCR_HIDDEN int pcr_read_fail(pcr_ctx* ctx);
 // normals (n,3) / FPFH (n,33) of a device cloud, by row (a grid build inside synchronises once)
 PCR_HIDDEN int pcr_hybrid_normals_device(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, int max_nn, int orient, const double* viewpoint, double* d_normals);
 PCR_HIDDEN int pcr_fpfh_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_normals, double radius, int max_nn, double* d_out);
+// FPFH of the m caller rows d_rows (device; any order, repeats allowed) -> d_out (m,33): bit for bit those rows of pcr_fpfh_device's
+// output, from the SPFH of the rows their lists reach only.  *d_n_spfh (device word, not null): how many rows that were.  Enqueued.
+PCR_HIDDEN int pcr_fpfh_rows_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_normals, double radius, int max_nn, const long long* d_rows, long long m,
+                                    double* d_out, unsigned int* d_n_spfh);
 // normals (towards the origin), SPFH and FPFH of every down-sampled point of a chunk: d_fpfh (ng,33)
 PCR_HIDDEN int pcr_scans_features(pcr_ctx* ctx, const scans_view& V, size_t ng, const pcr_global_params* g, const scans_scratch& w, double* d_fpfh);
 // ---- pcr_match.hip

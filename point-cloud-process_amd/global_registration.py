@@ -17,7 +17,7 @@ from .device import DeviceCloud, TargetIndex, default_context, points_of
 from .registration import PointCloud, read_bin_velodyne
 
 __all__ = [
-    "Feature", "RegistrationResult", "voxel_down_sample", "voxel_down_sample_device", "estimate_normals_hybrid", "estimate_normals_radius", "compute_fpfh_feature", "find_matchings",
+    "Feature", "RegistrationResult", "voxel_down_sample", "voxel_down_sample_device", "estimate_normals_hybrid", "estimate_normals_radius", "compute_fpfh_feature", "compute_fpfh_at_rows", "find_matchings",
     "registration_ransac_based_on_feature_matching", "preprocess_point_cloud", "prepare_dataset", "execute_global_registration",
     "ransac_init",
 ]
@@ -222,6 +222,37 @@ def compute_fpfh_feature(points, normals=None, radius=10.0, max_nn=100, ctx=None
     if own is not None:
         own.free()
     return Feature(out.T)
+
+
+def compute_fpfh_at_rows(points, rows, normals=None, radius=10.0, max_nn=100, ctx=None, return_info=False):
+    """FPFH of the caller rows ``rows`` only -- keypoints described over the whole cloud as search surface -> Feature with ``.data``
+    (33, m).  Column i is, bit for bit, column ``rows[i]`` of ``compute_fpfh_feature(points, normals, radius, max_nn)``; ``rows`` may
+    be in any order and may repeat.  Only the rows that the chosen rows' neighbour lists reach get an SPFH, so scratch and time follow
+    ``m * max_nn``, not the cloud's size.  ``return_info`` adds {"n_spfh": rows whose SPFH was computed, "n": cloud rows, "m": len(rows)}."""
+    ctx = ctx or default_context()
+    if normals is None:
+        normals = getattr(points, "normals", None)
+    if normals is None:
+        raise ValueError("compute_fpfh_at_rows needs normals (Open3D raises too when the cloud has none)")
+    rows = np.asarray(rows)
+    if rows.size and not np.issubdtype(rows.dtype, np.integer):
+        raise ValueError("rows must be integers")
+    rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+    cloud, own = _cloud(points, ctx)
+    try:
+        nrm = L.as_f64(np.asarray(normals, dtype=np.float64).reshape(-1, 3))
+        if nrm.shape[0] != cloud.n:
+            raise ValueError("normals do not match the cloud")
+        if rows.size and (rows.min() < 0 or rows.max() >= cloud.n):
+            raise ValueError(f"rows must lie in [0, {cloud.n})")
+        out = np.empty((len(rows), 33), dtype=np.float64)
+        n_spfh = C.c_int64(0)
+        L.check(L.lib().pcr_fpfh_rows(ctx.handle, cloud.handle, L.dptr(nrm), float(radius), int(max_nn), L.lptr(rows), len(rows), L.dptr(out), C.byref(n_spfh)), ctx.handle)
+    finally:
+        if own is not None:
+            own.free()
+    feature = Feature(out.T)
+    return (feature, {"n_spfh": int(n_spfh.value), "n": int(cloud.n), "m": len(rows)}) if return_info else feature
 
 
 def _match(a, b, ctx):
