@@ -341,6 +341,50 @@ PCR_API int pcr_iss_pcl(pcr_ctx* ctx, const pcr_cloud* cloud, double salient_rad
                         double gamma32, int min_neighbors, double* e3_out /* n */, int32_t* counts_out /* n */,
                         int32_t* keypoints_out, int64_t capacity, int64_t* n_keypoints_out);
 
+/* PCL-rule descriptors of the same module: featureFPFH33(pointcloud, keypoints, compute_normal_k, feature_radius) and
+ * featureFPFH33WithNormal(pointcloud, normals, keypoints, feature_radius) (keypoints.cpp:112-184,272-281) are pcr_normals_knn followed
+ * by pcr_fpfh_pcl, or pcr_fpfh_pcl alone.  As for the keypoints, the rules below ARE the definition (restated in NumPy by
+ * tests/pcl_fpfh_checks.py); parity with PCL's binary32 output is unpinned.  The conventions of the section hold: binary64 on the
+ * stored coordinates, per-row arrays by caller row, results independent of the lay-out of the records, PCR_E_UNSUPPORTED for a cloud
+ * whose extent exceeds 2^18 radii.  pcr_fpfh / pcr_fpfh_rows follow Open3D's rules (hybrid neighbourhood, max_nn cap, the row's own
+ * SPFH added on top) and are other descriptors.
+ *
+ * Ball: B(x) = the surface rows j with (dx*dx + dy*dy) + dz*dz <= r*r, d = p_j - x: the predicate above.  No cap: a ball may hold
+ *   every row of the cloud.
+ *
+ * k-NN normals (pcr_normals_knn: NormalEstimation with setKSearch(k), viewpoint vp; NULL: the origin): the neighbourhood of row i is its
+ *   k nearest rows, itself included, ordered by (distance, row) -- pcr_normals' neighbourhood, and its covariance; the normal is the
+ *   unit eigenvector of the covariance's smallest eigenvalue, flipped so that n . (vp - p_i) >= 0; curvature = e_min / (e0 + e1 + e2),
+ *   and 0 when that sum is 0.  A neighbourhood of fewer than 3 rows (a cloud of n < 3 rows): NaN, normal and curvature.  Supported:
+ *   3 <= k <= 16, what the exact batched k-NN supports; any other k: PCR_E_UNSUPPORTED with a message (pcr_last_error).
+ *
+ * SPFH of surface row i, from per-row normals (n x 3 by caller row; rows without one hold a non-finite value): K = |B(p_i)|.  Every
+ *   j in B(p_i) with j != i (by row number) forms a pair (p_i, n_i, p_j, n_j) with the Darboux-frame features of pcr_fpfh's SPFH --
+ *   d = p_j - p_i, a1 = n_i.d/|d|, a2 = n_j.d/|d|; if |a1| < |a2| the pair is swapped (u = n_j, w = n_i, d = -d, f2 = -a2), else
+ *   u = n_i, w = n_j, f2 = a1; v = (d x u)/|d x u|; f1 = v.w; f0 = atan2((u x v).w, u.w), written in that order.  The pair is SKIPPED
+ *   -- not binned -- when |d| == 0, when |d x u| == 0, or when a component of n_i or n_j is not finite.  Otherwise it adds 1 to the bins
+ *     clamp(floor(11 (f0 + pi) / (2 pi))),  11 + clamp(floor(11 (f1 + 1) 0.5)),  22 + clamp(floor(11 (f2 + 1) 0.5)),  clamp to 0..10.
+ *   With c_b the integer count of bin b: spfh_i[b] = c_b * (100.0 / (K - 1)) -- one product, one rounding -- and 0 when K == 1.
+ *   K counts every row of the ball, skipped pairs included.
+ *
+ * FPFH33 at keypoint x (any coordinates, on the surface or not): F[b] = sum over j in B(x) with d2_j != 0 of spfh_j[b] / d2_j (a true
+ *   division, d2_j = the predicate's left side); per block of 11 bins, with s the sum of the block's F in bin order,
+ *   out[b] = F[b] * (s != 0 ? 100.0 / s : 0.0).  The keypoint's own SPFH is NOT added.  An empty B(x), or an x with a component that is
+ *   not finite: 33 NaN (counts_out 0).  A ball that holds only rows at distance 0: 33 zeros.  A keypoint outside the cloud's box meets
+ *   empty space like any other.  The sum over j runs in a fixed order that is a function of the surface in caller-row order and of
+ *   the radius only (the grid cells of size r in a fixed order around x's cell, caller-row order within a cell): not of m, not of
+ *   the other keypoints, not of the lay-out of the records.  A call is repeatable to the bit.
+ *
+ * pcr_fpfh_pcl: surface = the cloud; normals (n,3) by caller row and keypoints (m,3), both on the host; features_out (m,33) row-major
+ *   binary64 (PCL's float is this rounded once); counts_out (m, may be NULL) = |B(x)|; *n_spfh_out (may be NULL) = M, the rows whose
+ *   SPFH was computed: the size of the union of the keypoints' balls.  NULL handles or arrays, m < 0, or a radius that is not a finite
+ *   positive number: PCR_E_INVALID before anything is launched or allocated.  m == 0: PCR_OK, nothing written, *n_spfh_out = 0.       */
+PCR_API int pcr_normals_knn(pcr_ctx* ctx, const pcr_cloud* cloud, int k, const double* viewpoint /* 3, or NULL */, double* normals_out /* n*3 */,
+                            double* curvature_out /* n, or NULL */);
+PCR_API int pcr_fpfh_pcl(pcr_ctx* ctx, const pcr_cloud* surface, const double* normals /* (n,3) by caller row, host */,
+                         const double* keypoints /* (m,3), host */, int64_t m, double radius, double* features_out /* (m,33) binary64 */,
+                         int32_t* counts_out /* m, or NULL: |B(x)| */, int64_t* n_spfh_out /* or NULL: M */);
+
 /* ---------------------------------------------------------- PCA / normals
  * pcr_pca: Pca_and_Voxel_filter/pca_normal.py:10-36 PCA(data, sort=True):
  * eigen-decomposition of np.cov of the cloud (divisor n-1); eigvals_out

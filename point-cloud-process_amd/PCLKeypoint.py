@@ -141,8 +141,11 @@ def keypointSift(points, min_scale=0.1, n_octaves=6, n_scales_per_octave=10, min
 
 
 def _no_descriptor(name):
-    raise NotImplementedError(f"{name} needs PCL's own descriptor rules (its k-NN normals and binning are unpinned here); use compute_fpfh_feature for the "
-                              "Open3D-rule FPFH")
+    if name.startswith("featureFPFH33"):
+        raise NotImplementedError(f"{name} is not routed yet: the PCL-rule FPFH descriptor is pcl_features.fpfh33 / fpfh33_with_normal (same arguments), "
+                                  "compute_fpfh_feature the Open3D-rule one")
+    raise NotImplementedError(f"{name} needs PCL's own descriptor rules (its SHOT reference frames and binning are unpinned here); the PCL-rule FPFH descriptor "
+                              "is pcl_features.fpfh33")
 
 
 def featureFPFH33(pointcloud, keypoints, compute_normal_k=10, feature_radius=1.0):

@@ -371,6 +371,10 @@ SIGNATURES = {
     "pcr_harris3d": (C.c_int, [_vp, _vp, _dp, C.POINTER(HarrisParams), _dp, _ip, _ip, C.c_int64, _lp, _dp, _dp, _ip]),
     # (ctx, cloud, salient radius, non-max radius, gamma21, gamma32, min_neighbors, scores, counts, keypoints, capacity, n_keypoints)
     "pcr_iss_pcl": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, C.c_int64, _lp]),
+    # (ctx, cloud, k, viewpoint | NULL, normals, curvature | NULL)
+    "pcr_normals_knn": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _dp]),
+    # (ctx, surface, normals, keypoints, m, radius, features, counts | NULL, n_spfh | NULL)
+    "pcr_fpfh_pcl": (C.c_int, [_vp, _vp, _dp, _dp, C.c_int64, C.c_double, _dp, _ip, _lp]),
     "pcr_pca": (C.c_int, [_vp, _vp, _dp, _dp, _dp]),
     "pcr_normals": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _ip]),
     "pcr_normals_hybrid": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_int, _dp, _dp]),

@@ -3,6 +3,7 @@
 // gl, gl + IG, ... of the 27.  A lane meets its cells in that order and a cell's records in stored order: a sum taken inside
 // `f` runs in a fixed order.  Cells outside the representable range, or that the table does not hold, are empty.
 #pragma once
+#include <string>
 #include "pcr_grid_dev.h"
 
 constexpr int IG = 8;  // lanes per point
@@ -48,4 +49,25 @@ __device__ static inline int ball_lanes_sum(int v) {
 #pragma unroll
     for (int off = IG / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// (host) the grid whose 3x3x3 block covers a ball of `radius` and is of its size (pcr_iss's rule and refusal)
+// The index sorts stably by cell, so a cell's records keep the order of the cloud's: a cloud that a search has laid out along its
+// curve is indexed from a copy in caller-row order, and its sums then run in the very order of the cloud as uploaded (same bits).
+static inline int ball_grid(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, const char* who, pcr_index_guard& idx) {
+    const double cell_req = radius * (1.0 + 1e-9);
+    int rc;
+    pcr_dev_block b_rows(ctx);
+    pcr_cloud by_row = *cloud;
+    if (cloud->morton_sorted) {
+        if ((rc = b_rows.alloc(sizeof(pcr_pt) * cloud->n)) || (rc = pcr_cloud_rows(ctx, cloud, b_rows.as<pcr_pt>()))) return rc;
+        by_row.d = b_rows.as<pcr_pt>();
+        by_row.morton_sorted = false;
+    }
+    if ((rc = pcr_index_build(ctx, &by_row, PCR_INDEX_GRID, cell_req, &idx.h))) return rc;
+    if (idx->cell > cell_req || idx->cell < radius * (1.0 - 1e-12)) {
+        ctx->last_error = std::string(who) + ": the cloud's extent exceeds 2^18 radii; the grid cannot hold a cell of the radius";
+        return PCR_E_UNSUPPORTED;
+    }
+    return PCR_OK;
 }

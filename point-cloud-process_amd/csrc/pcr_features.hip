@@ -18,6 +18,7 @@
 #include "pcr_grid_dev.h"
 #include "pcr_linalg.h"
 #include "pcr_global_dev.h"
+#include "pcr_pair_features.h"
 
 struct __attribute__((aligned(16))) nb_entry {
     double d2;
@@ -262,39 +263,7 @@ __global__ void __launch_bounds__(256) normals_finish_kernel(scans_view V, long 
 }
 
 // ---------------------------------------------------------------------- SPFH
-// Darboux-frame pair features (Open3D ComputePairFeatures): f0 = atan2 angle, f1 = v.n2, f2 = n1.d/|d|
-__device__ static inline bool pair_features(const double p1[3], const double n1[3], const double p2[3], const double n2[3], double f[3]) {
-    double d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
-    const double len = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    f[0] = f[1] = f[2] = 0.0;
-    if (len == 0.0) return true;  // zero vector still lands in bins (5, 5, 5), like Open3D's Zero() return
-    const double a1 = ((n1[0] * d[0] + n1[1] * d[1]) + n1[2] * d[2]) / len;
-    const double a2 = ((n2[0] * d[0] + n2[1] * d[1]) + n2[2] * d[2]) / len;
-    double u[3], w2[3];
-    if (fabs(a1) < fabs(a2)) {  // acos(|a1|) > acos(|a2|): the frame is anchored at the point whose normal is closer to the line
-        u[0] = n2[0]; u[1] = n2[1]; u[2] = n2[2];
-        w2[0] = n1[0]; w2[1] = n1[1]; w2[2] = n1[2];
-        d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2];
-        f[2] = -a2;
-    } else {
-        u[0] = n1[0]; u[1] = n1[1]; u[2] = n1[2];
-        w2[0] = n2[0]; w2[1] = n2[1]; w2[2] = n2[2];
-        f[2] = a1;
-    }
-    double v[3] = {d[1] * u[2] - d[2] * u[1], d[2] * u[0] - d[0] * u[2], d[0] * u[1] - d[1] * u[0]};
-    const double vn = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    if (vn == 0.0) { f[2] = 0.0; return true; }
-    v[0] /= vn; v[1] /= vn; v[2] /= vn;
-    const double w[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-    f[1] = (v[0] * w2[0] + v[1] * w2[1]) + v[2] * w2[2];
-    f[0] = atan2((w[0] * w2[0] + w[1] * w2[1]) + w[2] * w2[2], (u[0] * w2[0] + u[1] * w2[1]) + u[2] * w2[2]);
-    return true;
-}
-
-__device__ static inline int clamp_bin(double x) {
-    int h = (int)floor(x);
-    return h < 0 ? 0 : (h > 10 ? 10 : h);
-}
+// (the Darboux frame pair_features and the bin rule clamp_bin: pcr_pair_features.h, shared with the PCL-rule SPFH of pcr_fpfh_pcl.hip)
 
 // Where ONE row's results go.  The full pass keeps every row's list for fpfh_kernel (LISTS); the rows pass (below) keeps only its
 // SPFH, in a compact block.  The destination and the list store are the only differences: the pair loop, the binning, the skip of
@@ -326,9 +295,11 @@ __device__ static bool spfh_body(const pcr_grid_view& gv, const pcr_pt& p, doubl
         const double n2[3] = {normals[3 * (long long)en.id], normals[3 * (long long)en.id + 1], normals[3 * (long long)en.id + 2]};
         double f[3];
         pair_features(p1, n1, p2, n2, f);
-        atomicAdd(&hist[clamp_bin(11.0 * (f[0] + M_PI) / (2.0 * M_PI))], 1);
-        atomicAdd(&hist[11 + clamp_bin(11.0 * (f[1] + 1.0) * 0.5)], 1);
-        atomicAdd(&hist[22 + clamp_bin(11.0 * (f[2] + 1.0) * 0.5)], 1);
+        int bins[3];
+        pair_bins(f, bins);
+        atomicAdd(&hist[bins[0]], 1);
+        atomicAdd(&hist[bins[1]], 1);
+        atomicAdd(&hist[bins[2]], 1);
     }
     __syncthreads();
     if (LISTS && threadIdx.x == 0) *out.nb_cnt = cnt;

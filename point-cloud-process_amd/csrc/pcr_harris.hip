@@ -228,27 +228,6 @@ __global__ void __launch_bounds__(64) harris_refine_kernel(pcr_grid_view gv, con
     }
 }
 
-// the grid whose 3x3x3 block covers a ball of `radius` and is of its size (pcr_iss's rule and refusal)
-// The index sorts stably by cell, so a cell's records keep the order of the cloud's: a cloud that a search has laid out along its
-// curve is indexed from a copy in caller-row order, and its sums then run in the very order of the cloud as uploaded (same bits).
-static int harris_grid(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, const char* who, pcr_index_guard& idx) {
-    const double cell_req = radius * (1.0 + 1e-9);
-    int rc;
-    pcr_dev_block b_rows(ctx);
-    pcr_cloud by_row = *cloud;
-    if (cloud->morton_sorted) {
-        if ((rc = b_rows.alloc(sizeof(pcr_pt) * cloud->n)) || (rc = pcr_cloud_rows(ctx, cloud, b_rows.as<pcr_pt>()))) return rc;
-        by_row.d = b_rows.as<pcr_pt>();
-        by_row.morton_sorted = false;
-    }
-    if ((rc = pcr_index_build(ctx, &by_row, PCR_INDEX_GRID, cell_req, &idx.h))) return rc;
-    if (idx->cell > cell_req || idx->cell < radius * (1.0 - 1e-12)) {
-        ctx->last_error = std::string(who) + ": the cloud's extent exceeds 2^18 radii; the grid cannot hold a cell of the radius";
-        return PCR_E_UNSUPPORTED;
-    }
-    return PCR_OK;
-}
-
 // the flagged rows in ascending row -> b_rows (device, n ints), their number -> *n_sel and *n_keypoints_out, the rows themselves -> keypoints_out;
 // a buffer that cannot hold them: the needed count and PCR_E_UNSUPPORTED
 static int harris_select(pcr_ctx* ctx, int64_t n, const unsigned char* d_flags, const char* who, pcr_dev_block& b_rows, int32_t* keypoints_out, int64_t capacity,
@@ -287,7 +266,7 @@ extern "C" int pcr_normals_radius(pcr_ctx* ctx, const pcr_cloud* cloud, double r
     hipSetDevice(ctx->device);
     const int64_t n = cloud->n;
     pcr_index_guard idx(ctx);
-    int rc = harris_grid(ctx, cloud, radius, "pcr_normals_radius", idx);
+    int rc = ball_grid(ctx, cloud, radius, "pcr_normals_radius", idx);
     if (rc) return rc;
     pcr_dev_block b_nrm(ctx), b_counts(ctx);
     if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n)))) return rc;
@@ -315,7 +294,7 @@ extern "C" int pcr_harris3d(pcr_ctx* ctx, const pcr_cloud* cloud, const double* 
     const int64_t n = cloud->n;
     const bool nms = params->nms != 0, refine = nms && params->refine != 0 && refined_out;
     pcr_index_guard idx(ctx);
-    int rc = harris_grid(ctx, cloud, radius, "pcr_harris3d", idx);
+    int rc = ball_grid(ctx, cloud, radius, "pcr_harris3d", idx);
     if (rc) return rc;
     pcr_dev_block b_nrm(ctx), b_resp(ctx), b_counts(ctx);
     if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (rc = b_resp.alloc(sizeof(double) * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n)))) return rc;
@@ -390,7 +369,7 @@ extern "C" int pcr_iss_pcl(pcr_ctx* ctx, const pcr_cloud* cloud, double salient_
     const int64_t n = cloud->n;
     // one grid serves both radii: the 3x3x3 block of a cell of the larger radius covers either ball
     pcr_index_guard idx(ctx);
-    int rc = harris_grid(ctx, cloud, salient_radius > non_max_radius ? salient_radius : non_max_radius, "pcr_iss_pcl", idx);
+    int rc = ball_grid(ctx, cloud, salient_radius > non_max_radius ? salient_radius : non_max_radius, "pcr_iss_pcl", idx);
     if (rc) return rc;
     pcr_dev_block b_score(ctx), b_counts(ctx), b_flags(ctx), b_rows(ctx);
     if ((rc = b_score.alloc(sizeof(double) * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n))) || (rc = b_flags.alloc((size_t)n))) return rc;
