@@ -14,10 +14,10 @@
 #include <cfloat>
 #include <cmath>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include "pcr_grid_dev.h"
 #include "pcr_linalg.h"
 #include "pcr_global_dev.h"
+#include "pcr_sort.h"
 #include "pcr_pair_features.h"
 
 struct __attribute__((aligned(16))) nb_entry {
@@ -34,6 +34,9 @@ __device__ static inline bool nb_less(const nb_entry& a, const nb_entry& b) { re
 // stride over the concatenation, so a scan is ceil(points / 64) round trips whatever the cells' sizes.
 // CAP < NB_CAP: a block with a small candidate array (more blocks per CU); a sphere that holds more returns -2 and the point is done
 // again by the block with the full array.
+// (The cell lookup and the ballot compaction below are this function's own copies of ball_cell_run / wave_compact_slot of
+// pcr_ball_visit.h: with either of them called from here the same registers are allocated differently and hybrid_normals_kernel
+// measured 1.6 % slower on the 120 000-point scan (8.57 against 8.43 ms, medians of five alternating processes) -- profiles/ball_walk_resources.md.)
 template <int CAP>
 struct hybrid_lds_t {
     nb_entry nb[CAP];
@@ -195,7 +198,7 @@ __device__ static bool normals_body(const pcr_grid_view& gv, const pcr_pt& p, do
             c[3] += x * x; c[4] += x * y; c[5] += x * z; c[6] += y * y; c[7] += y * z; c[8] += z * z;
         }
 #pragma unroll
-        for (int k = 0; k < 9; ++k) c[k] = wave_sum(c[k]) / (double)cnt;
+        for (int k = 0; k < 9; ++k) c[k] = wave_sum_all(c[k]) / (double)cnt;
         S[0] = c[3] - c[0] * c[0]; S[1] = c[4] - c[0] * c[1]; S[2] = c[5] - c[0] * c[2];
         S[3] = c[6] - c[1] * c[1]; S[4] = c[7] - c[1] * c[2]; S[5] = c[8] - c[2] * c[2];
     }
@@ -579,9 +582,6 @@ int pcr_fpfh_rows_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_n
         (rc = spfh.alloc(sizeof(double) * 33 * bound)) || (rc = nbid.alloc(sizeof(unsigned int) * (size_t)max_nn * m)) || (rc = nbd2.alloc(sizeof(double) * (size_t)max_nn * m)) ||
         (rc = nbcnt.alloc(sizeof(int) * m)))
         return rc;
-    size_t tb = 0;
-    PCR_HIP(ctx, rocprim::select(nullptr, tb, rocprim::counting_iterator<unsigned int>(0u), need.as<unsigned int>(), marked.as<unsigned int>(), d_n_spfh, (size_t)n, ctx->stream));
-    if ((rc = tmp.alloc(tb > 0 ? tb : 16))) return rc;
     hybrid_space sp(ctx);
     if ((rc = sp.open(cloud, radius))) return rc;
     const bool table = sp.idx != nullptr;   // (an index's records are in its own order; brute_view's are in row order)
@@ -591,7 +591,7 @@ int pcr_fpfh_rows_device(pcr_ctx* ctx, const pcr_cloud* cloud, const double* d_n
     const unsigned int* const pos = table ? rowpos.as<unsigned int>() : nullptr;
     hipLaunchKernelGGL(fpfh_rows_lists_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, sp.view, n, pos, radius * radius, max_nn, d_rows, m, need.as<unsigned int>(),
                        nbid.as<unsigned int>(), nbd2.as<double>(), nbcnt.as<int>(), fail_word(ctx));
-    PCR_HIP(ctx, rocprim::select(tmp.p, tb, rocprim::counting_iterator<unsigned int>(0u), need.as<unsigned int>(), marked.as<unsigned int>(), d_n_spfh, (size_t)n, ctx->stream));
+    if ((rc = pcr_select_positions(ctx, need.as<unsigned int>(), (size_t)n, marked.as<unsigned int>(), d_n_spfh, tmp))) return rc;
     hipLaunchKernelGGL(spfh_rows_kernel, dim3((unsigned)bound), dim3(64), 0, ctx->stream, sp.view, pos, radius * radius, max_nn, d_normals, (const unsigned int*)marked.as<unsigned int>(),
                        (const unsigned int*)d_n_spfh, need.as<unsigned int>(), spfh.as<double>(), fail_word(ctx));
     hipLaunchKernelGGL(fpfh_rows_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, n, m, max_nn, d_rows, (const double*)spfh.as<double>(), (const unsigned int*)need.as<unsigned int>(),

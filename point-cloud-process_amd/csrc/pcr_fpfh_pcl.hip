@@ -3,9 +3,9 @@
 // coordinates searched against the cloud as search surface, the neighbourhood is the radius ball alone and has no cap, the weighted
 // sum is normalised and nothing is added to it.
 // The surface is indexed by the grid with cell = radius over a caller-row-order copy (ball_grid), so a ball lies in the 3x3x3 block of
-// its centre's cell and a cell's records stand in caller-row order.  A ball is WALKED, never stored: one wave per centre, lanes 0..26
-// look one cell of the block up each, the wave then takes the 27 runs one after the other, 64 records a trip.  Four stages on the
-// stream, nothing read back between them:
+// its centre's cell and a cell's records stand in caller-row order.  A ball is WALKED, never stored: one wave per centre, by the wave
+// walk of pcr_ball_visit.h (the 27 runs one after the other, 64 records a trip).  Four stages on the stream, nothing read back
+// between them:
 //   mark      wave per keypoint: need[position] = 1 for the records of its ball (plain stores of one constant), the ball's size
 //   compact   rocprim::select over the positions: the marked records in ascending position, their number M on the device
 //   SPFH      wave per marked record: the in-ball positions of a trip are compacted into LDS (ballot + prefix) and the pair features
@@ -19,36 +19,12 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <rocprim/rocprim.hpp>
 #include "pcr_ball_visit.h"
 #include "pcr_pair_features.h"
+#include "pcr_sort.h"
 
 constexpr int SP_STAGE = 128;   // staged in-ball positions of the SPFH pass: < 64 left over + <= 64 of a trip
 constexpr int FP_STAGE = 256;   // staged (slot, d^2) of the FPFH pass, consumed when another trip might not fit
-
-__device__ static inline bool finite3(double x, double y, double z) { return x - x == 0.0 && y - y == 0.0 && z - z == 0.0; }
-
-// lanes 0..26: the run [s, e) of cell `lane` of the 3x3x3 block around (x, y, z); an empty run for the other lanes, for cells outside the
-// representable range or absent from the table, and for a centre that is not finite
-__device__ static inline void block_runs(const pcr_grid_view& gv, double x, double y, double z, int lane, unsigned int* s, unsigned int* e) {
-    *s = *e = 0;
-    if (lane >= 27) return;
-    bool clamped = false;
-    const int ix = cell_coord(x, gv.lo[0], gv.inv_cell0, &clamped), iy = cell_coord(y, gv.lo[1], gv.inv_cell0, &clamped), iz = cell_coord(z, gv.lo[2], gv.inv_cell0, &clamped);
-    const unsigned int nx = (unsigned int)(ix + lane % 3 - 1), ny = (unsigned int)(iy + (lane / 3) % 3 - 1), nz = (unsigned int)(iz + lane / 9 - 1);
-    unsigned int cs = 0, ce = 0;
-    if (!clamped && nx <= (unsigned int)PCR_COORD_MAX && ny <= (unsigned int)PCR_COORD_MAX && nz <= (unsigned int)PCR_COORD_MAX &&
-        lookup_cell(gv.table[0], gv.mask[0], nx, ny, nz, &cs, &ce)) {
-        *s = cs;
-        *e = ce;
-    }
-}
-
-__device__ static inline int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(64) pcl_mark_kernel(pcr_grid_view gv, const double* __restrict__ kp /* (m,3) */, double r2, unsigned int* __restrict__ need /* by position, zeroed */,
                                                       int* __restrict__ counts /* (m) */) {
@@ -56,14 +32,13 @@ __global__ void __launch_bounds__(64) pcl_mark_kernel(pcr_grid_view gv, const do
     const long long i = blockIdx.x;
     const double x = kp[3 * i], y = kp[3 * i + 1], z = kp[3 * i + 2];
     unsigned int s, e;
-    block_runs(gv, x, y, z, lane, &s, &e);
+    wave_block_runs(gv, x, y, z, lane, &s, &e);
     int c = 0;
-    for (int cell = 0; cell < 27; ++cell) {
-        const unsigned int cs = __shfl(s, cell, 64), ce = __shfl(e, cell, 64);
-        for (unsigned int j = cs + lane; j < ce; j += 64)
-            if (dist2(x, y, z, gv.pts[j]) <= r2) { need[j] = 1u; ++c; }
-    }
-    c = wave_sum(c);
+    auto f = [&](unsigned int j, bool valid) {
+        if (valid && dist2(x, y, z, gv.pts[j]) <= r2) { need[j] = 1u; ++c; }
+    };
+    wave_visit_runs(s, e, lane, f);
+    c = wave_sum_all(c);
     if (lane == 0) counts[i] = c;
 }
 
@@ -98,27 +73,24 @@ __global__ void __launch_bounds__(64) pcl_spfh_kernel(pcr_grid_view gv, double r
         atomicAdd(&hist[bins[2]], 1);
     };
     unsigned int s, e;
-    block_runs(gv, p.x, p.y, p.z, lane, &s, &e);
+    wave_block_runs(gv, p.x, p.y, p.z, lane, &s, &e);
     int staged = 0, K = 0;   // (the same in every lane)
     __syncthreads();
-    for (int cell = 0; cell < 27; ++cell) {
-        const unsigned int cs = __shfl(s, cell, 64), ce = __shfl(e, cell, 64);
-        for (unsigned int j0 = cs; j0 < ce; j0 += 64) {
-            const unsigned int j = j0 + lane;
-            const bool in = j < ce && dist2(p.x, p.y, p.z, gv.pts[j]) <= r2;
-            const unsigned long long mask = __ballot(in);
-            const int add = __popcll(mask);
-            if (in) s_pos[staged + __popcll(mask & ((1ull << lane) - 1ull))] = j;
-            staged += add;
-            K += add;
-            if (staged >= 64) {
-                __syncthreads();
-                pair(s_pos[staged - 64 + lane]);
-                staged -= 64;
-                __syncthreads();
-            }
+    auto trip = [&](unsigned int j, bool valid) {
+        const bool in = valid && dist2(p.x, p.y, p.z, gv.pts[j]) <= r2;
+        int add;
+        const int at = staged + wave_compact_slot(in, lane, &add);
+        if (in) s_pos[at] = j;
+        staged += add;
+        K += add;
+        if (staged >= 64) {
+            __syncthreads();
+            pair(s_pos[staged - 64 + lane]);
+            staged -= 64;
+            __syncthreads();
         }
-    }
+    };
+    wave_visit_runs(s, e, lane, trip);
     __syncthreads();
     if (lane < staged) pair(s_pos[lane]);
     __syncthreads();
@@ -138,7 +110,7 @@ __global__ void __launch_bounds__(64) pcl_fpfh_kernel(pcr_grid_view gv, const do
     }
     const double x = kp[3 * i], y = kp[3 * i + 1], z = kp[3 * i + 2];
     unsigned int s, e;
-    block_runs(gv, x, y, z, lane, &s, &e);
+    wave_block_runs(gv, x, y, z, lane, &s, &e);
     int staged = 0;   // (the same in every lane)
     double acc = 0.0;
     // lane = bin: the staged terms in their order, the SPFH rows of eight entries requested together
@@ -154,31 +126,28 @@ __global__ void __launch_bounds__(64) pcl_fpfh_kernel(pcr_grid_view gv, const do
         }
         for (; t < staged; ++t) acc += spfh[33 * (size_t)s_slot[t] + lane] / s_d2[t];
     };
-    for (int cell = 0; cell < 27; ++cell) {
-        const unsigned int cs = __shfl(s, cell, 64), ce = __shfl(e, cell, 64);
-        for (unsigned int j0 = cs; j0 < ce; j0 += 64) {
-            const unsigned int j = j0 + lane;
-            double d2 = 0.0;
-            bool in = false;
-            if (j < ce) {
-                d2 = dist2(x, y, z, gv.pts[j]);
-                in = d2 <= r2 && d2 != 0.0;   // (a row at distance 0 is in the ball and adds nothing)
-            }
-            const unsigned long long mask = __ballot(in);
-            if (in) {
-                const int at = staged + __popcll(mask & ((1ull << lane) - 1ull));
-                s_slot[at] = slot[j];
-                s_d2[at] = d2;
-            }
-            staged += __popcll(mask);
-            if (staged + 64 > FP_STAGE) {
-                __syncthreads();
-                consume();
-                staged = 0;
-                __syncthreads();
-            }
+    auto trip = [&](unsigned int j, bool valid) {
+        double d2 = 0.0;
+        bool in = false;
+        if (valid) {
+            d2 = dist2(x, y, z, gv.pts[j]);
+            in = d2 <= r2 && d2 != 0.0;   // (a row at distance 0 is in the ball and adds nothing)
         }
-    }
+        int add;
+        const int at = staged + wave_compact_slot(in, lane, &add);
+        if (in) {
+            s_slot[at] = slot[j];
+            s_d2[at] = d2;
+        }
+        staged += add;
+        if (staged + 64 > FP_STAGE) {
+            __syncthreads();
+            consume();
+            staged = 0;
+            __syncthreads();
+        }
+    };
+    wave_visit_runs(s, e, lane, trip);
     __syncthreads();
     consume();
     if (lane < 33) s_acc[lane] = acc;
@@ -208,15 +177,9 @@ extern "C" int pcr_fpfh_pcl(pcr_ctx* ctx, const pcr_cloud* surface, const double
     // second host wait into the call (264 n bytes from the arena instead of 264 M; blocks k >= M of the SPFH launch leave at once).
     pcr_dev_block b_nrm(ctx), b_kp(ctx), b_need(ctx), b_marked(ctx), b_m(ctx), b_spfh(ctx), b_counts(ctx), b_out(ctx), b_tmp(ctx);
     if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (rc = b_kp.alloc(sizeof(double) * 3 * m)) || (rc = b_need.alloc(sizeof(unsigned int) * n)) ||
-        (rc = b_marked.alloc(sizeof(unsigned int) * n)) || (rc = b_m.alloc(16)) || (rc = b_counts.alloc(sizeof(int) * m)) || (rc = b_out.alloc(sizeof(double) * 33 * m)))
+        (rc = b_marked.alloc(sizeof(unsigned int) * n)) || (rc = b_m.alloc(16)) || (rc = b_counts.alloc(sizeof(int) * m)) || (rc = b_out.alloc(sizeof(double) * 33 * m)) ||
+        (rc = b_spfh.alloc(sizeof(double) * 33 * n)))
         return rc;
-#ifndef PCR_FPFH_PCL_READ_M
-    if ((rc = b_spfh.alloc(sizeof(double) * 33 * n))) return rc;
-#endif
-    size_t tb = 0;
-    PCR_HIP(ctx, rocprim::select(nullptr, tb, rocprim::counting_iterator<unsigned int>(0u), b_need.as<unsigned int>(), b_marked.as<unsigned int>(), b_m.as<unsigned int>(), (size_t)n,
-                                 ctx->stream));
-    if ((rc = b_tmp.alloc(tb > 0 ? tb : 16))) return rc;
     const double r2 = radius * radius;
     PCR_HIP(ctx, hipMemcpyAsync(b_nrm.p, normals, sizeof(double) * 3 * n, hipMemcpyHostToDevice, ctx->stream));
     PCR_HIP(ctx, hipMemcpyAsync(b_kp.p, keypoints, sizeof(double) * 3 * m, hipMemcpyHostToDevice, ctx->stream));
@@ -224,18 +187,9 @@ extern "C" int pcr_fpfh_pcl(pcr_ctx* ctx, const pcr_cloud* surface, const double
     pcr_prof_mark(ctx, 0);
     hipLaunchKernelGGL(pcl_mark_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, idx->view, (const double*)b_kp.p, r2, b_need.as<unsigned int>(), b_counts.as<int>());
     pcr_prof_mark(ctx, 1);
-    PCR_HIP(ctx, rocprim::select(b_tmp.p, tb, rocprim::counting_iterator<unsigned int>(0u), b_need.as<unsigned int>(), b_marked.as<unsigned int>(), b_m.as<unsigned int>(), (size_t)n,
-                                 ctx->stream));
+    if ((rc = pcr_select_positions(ctx, b_need.as<unsigned int>(), (size_t)n, b_marked.as<unsigned int>(), b_m.as<unsigned int>(), b_tmp))) return rc;
     pcr_prof_mark(ctx, 2);
-    unsigned spfh_blocks = (unsigned)n;
-#ifdef PCR_FPFH_PCL_READ_M   // (A/B build, scripts/pcl_fpfh_bench.py: the block sized by M at the price of a host wait here)
-    {
-        unsigned int m_now = 0;
-        if ((rc = pcr_d2h_small(ctx, &m_now, b_m.p, sizeof(unsigned int))) || (rc = b_spfh.alloc(sizeof(double) * 33 * (m_now > 0 ? m_now : 1)))) return rc;
-        spfh_blocks = m_now > 0 ? m_now : 1;
-    }
-#endif
-    hipLaunchKernelGGL(pcl_spfh_kernel, dim3(spfh_blocks), dim3(64), 0, ctx->stream, idx->view, r2, (const double*)b_nrm.p, (const unsigned int*)b_marked.p,
+    hipLaunchKernelGGL(pcl_spfh_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, idx->view, r2, (const double*)b_nrm.p, (const unsigned int*)b_marked.p,
                        (const unsigned int*)b_m.p, b_need.as<unsigned int>(), b_spfh.as<double>());
     pcr_prof_mark(ctx, 3);
     hipLaunchKernelGGL(pcl_fpfh_kernel, dim3((unsigned)m), dim3(64), 0, ctx->stream, idx->view, (const double*)b_kp.p, r2, (const unsigned int*)b_need.p,

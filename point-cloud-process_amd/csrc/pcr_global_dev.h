@@ -2,7 +2,7 @@
 // The library has no relocatable device code: a kernel is launched only by the unit that defines it, and the units meet in HOST functions
 // that enqueue on ctx->stream.  Nothing here synchronises unless it says so.
 #pragma once
-#include "pcr_internal.h"
+#include "pcr_wave.h"   // wave_sum_all
 
 constexpr int NB_CAP = 1024;
 // clouds of up to this many points are searched without an index (brute_view; the fused initialisation takes only such scans)
@@ -13,11 +13,6 @@ constexpr int RANSAC_FIRST = 4096, RANSAC_BATCH = 16384;
 inline int ransac_batch_size(long long done, int max_iteration) {
     const long long want = done == 0 ? RANSAC_FIRST : RANSAC_BATCH, left = max_iteration - done;
     return (int)(left < want ? left : want);
-}
-__device__ static inline double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 // The down-sampled scans of a chunk, one behind the other (pcr_voxel_downsample_scans): record v belongs to scan vsid[v], whose records
 // are [scan_first[s], scan_first[s + 1]) with id = row within the scan.  A block's "grid view" is its own scan, searched without an index.

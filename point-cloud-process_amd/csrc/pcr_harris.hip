@@ -1,7 +1,7 @@
 // Harris-3D and PCL-rule ISS keypoints -- the XYZ detectors of PCLKeypoints/src/keypoints.cpp (keypointHarris3D, keypointIss), by the
 // rules stated in include/pcr.h (PCL itself is not part of the build: parity with its binary32 output is unpinned).
-// All passes walk the radius neighbourhood the way pcr_iss.hip does (pcr_ball_visit.h: grid cell = radius, the 3x3x3 block, 8 lanes per
-// point, lane-owned cells; the note at the top of pcr_iss.hip says why per-point lanes and not wave tiles), in binary64, and every sum
+// All passes walk the radius neighbourhood by pcr_ball_visit.h (the lane-group walk, 8 lanes per point; the note at the top of
+// pcr_iss.hip says why per-point lanes and not wave tiles; refine: the wave walk), in binary64, and every sum
 // runs in a fixed order -- a lane's cells in lane order, a cell's records in stored order, then the lanes -- so a call is repeatable
 // to the bit.  Per-row results are stored BY CALLER ROW (the record's id): a cloud that an index has laid out along its curve takes
 // and returns caller rows like any other.
@@ -15,23 +15,21 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <rocprim/rocprim.hpp>
 #include "pcr_ball_visit.h"
 #include "pcr_linalg.h"
-
-__device__ static inline bool finite3(double x, double y, double z) { return x - x == 0.0 && y - y == 0.0 && z - z == 0.0; }
+#include "pcr_sort.h"
 
 template <bool SCATTER>
 __global__ void __launch_bounds__(256) harris_poscov_kernel(pcr_grid_view gv, long long n, double r2_in, double vx, double vy, double vz, double gamma21,
                                                             double gamma32, double* __restrict__ out /* by row: normals (n,3) | SCATTER: score (n) */,
                                                             int* __restrict__ counts /* by row, or null */) {
-    const int gl = threadIdx.x % IG;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / IG;
-    if (i >= n) return;
+    long long i;
+    int gl;
+    if (!ball_lane_point(n, &i, &gl)) return;
     const pcr_pt p = gv.pts[i];
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // x y z, xx xy xz yy yz zz
     int c = 0;
-    auto f = [&](const pcr_pt& b) {
+    auto f = [&](const pcr_pt& b, unsigned int) {
         const double dx = b.x - p.x, dy = b.y - p.y, dz = b.z - p.z;
         if ((dx * dx + dy * dy) + dz * dz <= r2_in) {
             ++c;
@@ -40,7 +38,7 @@ __global__ void __launch_bounds__(256) harris_poscov_kernel(pcr_grid_view gv, lo
             m[6] += dy * dy; m[7] += dy * dz; m[8] += dz * dz;
         }
     };
-    iss_visit_block(gv, p.x, p.y, p.z, gl, f);
+    ball_visit<BALL_LANES>(gv, p.x, p.y, p.z, gl, f);
 #pragma unroll
     for (int k = SCATTER ? 3 : 0; k < 9; ++k) m[k] = ball_lanes_sum(m[k]);
     c = ball_lanes_sum(c);
@@ -82,13 +80,13 @@ __global__ void __launch_bounds__(256) harris_poscov_kernel(pcr_grid_view gv, lo
 
 __global__ void __launch_bounds__(256) harris_response_kernel(pcr_grid_view gv, long long n, double r2_in, const double* __restrict__ nrm /* by row (n,3) */,
                                                               double* __restrict__ resp /* by row */, int* __restrict__ counts /* by row, or null */) {
-    const int gl = threadIdx.x % IG;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / IG;
-    if (i >= n) return;
+    long long i;
+    int gl;
+    if (!ball_lane_point(n, &i, &gl)) return;
     const pcr_pt p = gv.pts[i];
     double m[6] = {0, 0, 0, 0, 0, 0};   // xx xy xz yy yz zz of the normals
     int k = 0, c = 0;
-    auto f = [&](const pcr_pt& b) {
+    auto f = [&](const pcr_pt& b, unsigned int) {
         if (dist2(p.x, p.y, p.z, b) <= r2_in) {
             ++c;
             const double* q = nrm + 3 * b.id;
@@ -100,7 +98,7 @@ __global__ void __launch_bounds__(256) harris_response_kernel(pcr_grid_view gv, 
             }
         }
     };
-    iss_visit_block(gv, p.x, p.y, p.z, gl, f);
+    ball_visit<BALL_LANES>(gv, p.x, p.y, p.z, gl, f);
 #pragma unroll
     for (int j = 0; j < 6; ++j) m[j] = ball_lanes_sum(m[j]);
     k = ball_lanes_sum(k);
@@ -126,9 +124,9 @@ __global__ void __launch_bounds__(256) harris_response_kernel(pcr_grid_view gv, 
 __global__ void __launch_bounds__(256) harris_suppress_kernel(pcr_grid_view gv, long long n, double r2_in, const double* __restrict__ score /* by row */, double thr,
                                                               int strict, int min_nb, unsigned char* __restrict__ flags /* by row */,
                                                               int* __restrict__ counts /* by row, or null */, unsigned int* __restrict__ row_pos /* by row, or null */) {
-    const int gl = threadIdx.x % IG;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / IG;
-    if (i >= n) return;
+    long long i;
+    int gl;
+    if (!ball_lane_point(n, &i, &gl)) return;
     const pcr_pt p = gv.pts[i];
     const double s = score[p.id];
     const bool cand = strict ? s > thr : s >= thr;
@@ -138,13 +136,13 @@ __global__ void __launch_bounds__(256) harris_suppress_kernel(pcr_grid_view gv, 
         return;
     }
     int c = 0, beaten = 0;
-    auto f = [&](const pcr_pt& b) {
+    auto f = [&](const pcr_pt& b, unsigned int) {
         if (dist2(p.x, p.y, p.z, b) <= r2_in) {
             ++c;
             beaten += score[b.id] > s;
         }
     };
-    iss_visit_block(gv, p.x, p.y, p.z, gl, f);
+    ball_visit<BALL_LANES>(gv, p.x, p.y, p.z, gl, f);
     c = ball_lanes_sum(c);
     beaten = ball_lanes_sum(beaten);
     if (gl != 0) return;
@@ -168,42 +166,27 @@ __global__ void __launch_bounds__(64) harris_refine_kernel(pcr_grid_view gv, con
     int round = 0;
     while (round < 5) {
         double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // A: xx xy xz yy yz zz, b: x y z
-        // lanes 0..26 look one cell of the block up each; the wave then walks the 27 runs one after the other, lane l taking the
-        // records l, l + 64, ... of a run: a lane's terms come in a fixed order
-        unsigned int s = 0, e = 0;
-        if (lane < 27) {
-            bool clamped = false;
-            const int ix = cell_coord(cx, gv.lo[0], gv.inv_cell0, &clamped), iy = cell_coord(cy, gv.lo[1], gv.inv_cell0, &clamped),
-                      iz = cell_coord(cz, gv.lo[2], gv.inv_cell0, &clamped);
-            const unsigned int nx = (unsigned int)(ix + lane % 3 - 1), ny = (unsigned int)(iy + (lane / 3) % 3 - 1), nz = (unsigned int)(iz + lane / 9 - 1);
-            if (clamped || nx > (unsigned int)PCR_COORD_MAX || ny > (unsigned int)PCR_COORD_MAX || nz > (unsigned int)PCR_COORD_MAX ||
-                !lookup_cell(gv.table[0], gv.mask[0], nx, ny, nz, &s, &e))
-                s = e = 0;
-        }
-        for (int c = 0; c < 27; ++c) {
-            const unsigned int cs = __shfl(s, c, 64), ce = __shfl(e, c, 64);
-            for (unsigned int j = cs + lane; j < ce; j += 64) {
-                const pcr_pt b = gv.pts[j];
-                if (dist2(cx, cy, cz, b) <= r2_in) {
-                    const double* q = nrm + 3 * b.id;
-                    const double a0 = q[0], a1 = q[1], a2 = q[2];
-                    if (finite3(a0, a1, a2)) {
-                        const double xx = a0 * a0, xy = a0 * a1, xz = a0 * a2, yy = a1 * a1, yz = a1 * a2, zz = a2 * a2;
-                        m[0] += xx; m[1] += xy; m[2] += xz; m[3] += yy; m[4] += yz; m[5] += zz;
-                        m[6] += (xx * b.x + xy * b.y) + xz * b.z;
-                        m[7] += (xy * b.x + yy * b.y) + yz * b.z;
-                        m[8] += (xz * b.x + yz * b.y) + zz * b.z;
-                    }
+        // the wave walk of pcr_ball_visit.h: a lane's terms come in a fixed order
+        auto f = [&](unsigned int j, bool valid) {
+            if (!valid) return;
+            const pcr_pt b = gv.pts[j];
+            if (dist2(cx, cy, cz, b) <= r2_in) {
+                const double* q = nrm + 3 * b.id;
+                const double a0 = q[0], a1 = q[1], a2 = q[2];
+                if (finite3(a0, a1, a2)) {
+                    const double xx = a0 * a0, xy = a0 * a1, xz = a0 * a2, yy = a1 * a1, yz = a1 * a2, zz = a2 * a2;
+                    m[0] += xx; m[1] += xy; m[2] += xz; m[3] += yy; m[4] += yz; m[5] += zz;
+                    m[6] += (xx * b.x + xy * b.y) + xz * b.z;
+                    m[7] += (xy * b.x + yy * b.y) + yz * b.z;
+                    m[8] += (xz * b.x + yz * b.y) + zz * b.z;
                 }
             }
-        }
+        };
+        unsigned int s, e;
+        wave_block_runs(gv, cx, cy, cz, lane, &s, &e);
+        wave_visit_runs(s, e, lane, f);
 #pragma unroll
-        for (int k = 0; k < 9; ++k) {   // the 64 lanes in a fixed order; every lane ends with the same bits
-            double v = m[k];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-            m[k] = v;
-        }
+        for (int k = 0; k < 9; ++k) m[k] = wave_sum_all(m[k]);   // the 64 lanes in a fixed order; every lane ends with the same bits
         ++round;
         const double xx = m[0], xy = m[1], xz = m[2], yy = m[3], yz = m[4], zz = m[5];
         const double det = xx * yy * zz + 2.0 * xy * xz * yz - xz * xz * yy - xy * xy * zz - yz * yz * xx;
@@ -235,12 +218,7 @@ static int harris_select(pcr_ctx* ctx, int64_t n, const unsigned char* d_flags, 
     pcr_dev_block b_cnt(ctx), b_tmp(ctx);
     int rc;
     if ((rc = b_rows.alloc(sizeof(int) * n)) || (rc = b_cnt.alloc(sizeof(unsigned int)))) return rc;
-    size_t tb = 0;
-    hipError_t e = rocprim::select(nullptr, tb, rocprim::counting_iterator<int>(0), d_flags, b_rows.as<int>(), b_cnt.as<unsigned int>(), (size_t)n, ctx->stream);
-    if (e == hipSuccess && (rc = b_tmp.alloc(tb > 0 ? tb : 16)) == PCR_OK)
-        e = rocprim::select(b_tmp.p, tb, rocprim::counting_iterator<int>(0), d_flags, b_rows.as<int>(), b_cnt.as<unsigned int>(), (size_t)n, ctx->stream);
-    if (rc) return rc;
-    if (e != hipSuccess) { ctx->last_error = std::string(who) + " (select): " + hipGetErrorString(e); return PCR_E_HIP; }
+    if ((rc = pcr_select_positions(ctx, d_flags, (size_t)n, b_rows.as<int>(), b_cnt.as<unsigned int>(), b_tmp, who))) return rc;
     if ((rc = pcr_d2h_small(ctx, n_sel, b_cnt.p, sizeof(unsigned int)))) return rc;
     *n_keypoints_out = (int64_t)*n_sel;
     if ((int64_t)*n_sel > capacity) {
@@ -249,8 +227,6 @@ static int harris_select(pcr_ctx* ctx, int64_t n, const unsigned char* d_flags, 
     }
     return pcr_d2h_small(ctx, keypoints_out, b_rows.p, sizeof(int) * (size_t)*n_sel);
 }
-
-static inline unsigned harris_blocks(int64_t n) { return (unsigned)((n * IG + 255) / 256); }
 
 extern "C" void pcr_harris_default_params(pcr_harris_params* p) {
     if (!p) return;
@@ -271,7 +247,7 @@ extern "C" int pcr_normals_radius(pcr_ctx* ctx, const pcr_cloud* cloud, double r
     pcr_dev_block b_nrm(ctx), b_counts(ctx);
     if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n)))) return rc;
     const double vx = viewpoint ? viewpoint[0] : 0.0, vy = viewpoint ? viewpoint[1] : 0.0, vz = viewpoint ? viewpoint[2] : 0.0;
-    hipLaunchKernelGGL(harris_poscov_kernel<false>, dim3(harris_blocks(n)), dim3(256), 0, ctx->stream, idx->view, (long long)n, radius * radius, vx, vy, vz, 0.0, 0.0,
+    hipLaunchKernelGGL(harris_poscov_kernel<false>, dim3(ball_blocks(n)), dim3(256), 0, ctx->stream, idx->view, (long long)n, radius * radius, vx, vy, vz, 0.0, 0.0,
                        b_nrm.as<double>(), b_counts.as<int>());
     PCR_HIP(ctx, hipGetLastError());
     if ((rc = pcr_d2h_staged(ctx, normals_out, b_nrm.p, sizeof(double) * 3 * (size_t)n))) return rc;
@@ -299,7 +275,7 @@ extern "C" int pcr_harris3d(pcr_ctx* ctx, const pcr_cloud* cloud, const double* 
     pcr_dev_block b_nrm(ctx), b_resp(ctx), b_counts(ctx);
     if ((rc = b_nrm.alloc(sizeof(double) * 3 * n)) || (rc = b_resp.alloc(sizeof(double) * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n)))) return rc;
     const double r2_in = radius * radius;
-    const unsigned grid = harris_blocks(n);
+    const unsigned grid = ball_blocks(n);
     if (normals) PCR_HIP(ctx, hipMemcpyAsync(b_nrm.p, normals, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     else hipLaunchKernelGGL(harris_poscov_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, r2_in, 0.0, 0.0, 0.0, 0.0, 0.0, b_nrm.as<double>(),
                             (int*)nullptr);
@@ -373,7 +349,7 @@ extern "C" int pcr_iss_pcl(pcr_ctx* ctx, const pcr_cloud* cloud, double salient_
     if (rc) return rc;
     pcr_dev_block b_score(ctx), b_counts(ctx), b_flags(ctx), b_rows(ctx);
     if ((rc = b_score.alloc(sizeof(double) * n)) || (counts_out && (rc = b_counts.alloc(sizeof(int) * n))) || (rc = b_flags.alloc((size_t)n))) return rc;
-    const unsigned grid = harris_blocks(n);
+    const unsigned grid = ball_blocks(n);
     hipLaunchKernelGGL(harris_poscov_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, idx->view, (long long)n, salient_radius * salient_radius, 0.0, 0.0, 0.0, gamma21,
                        gamma32, b_score.as<double>(), (int*)nullptr);
     if (want_kp || counts_out)

@@ -21,18 +21,17 @@
 #include <string>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "pcr_ball_visit.h"   // iss_visit_block, IG lanes per point: shared with pcr_harris.hip
+#include "pcr_ball_visit.h"
 
 __global__ void __launch_bounds__(256) iss_count_kernel(pcr_grid_view gv, long long n, double r2_in, int* __restrict__ counts /* by row id */) {
-    const int gl = threadIdx.x % IG;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / IG;
-    if (i >= n) return;
+    long long i;
+    int gl;
+    if (!ball_lane_point(n, &i, &gl)) return;
     const pcr_pt p = gv.pts[i];
     int c = 0;
-    auto f = [&](const pcr_pt& b) { c += dist2(p.x, p.y, p.z, b) <= r2_in; };
-    iss_visit_block(gv, p.x, p.y, p.z, gl, f);
-#pragma unroll
-    for (int off = IG / 2; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    auto f = [&](const pcr_pt& b, unsigned int) { c += dist2(p.x, p.y, p.z, b) <= r2_in; };
+    ball_visit<BALL_LANES>(gv, p.x, p.y, p.z, gl, f);
+    c = ball_lanes_sum(c);
     if (gl == 0) counts[p.id] = c;
 }
 
@@ -83,12 +82,12 @@ __global__ void __launch_bounds__(256) iss_cov_kernel(pcr_grid_view gv, long lon
                                                       double* __restrict__ lambdas /* by row id, (n,3) */, double gamma21, double gamma32,
                                                       int* __restrict__ cand /* row ids passing the ratio tests, any order */,
                                                       unsigned int* __restrict__ cand_count, struct iss_cand* __restrict__ cand_rec /* or the records */) {
-    const int gl = threadIdx.x % IG;
-    const long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) / IG;
-    if (i >= n) return;
+    long long i;
+    int gl;
+    if (!ball_lane_point(n, &i, &gl)) return;
     const pcr_pt p = gv.pts[i];
     double m[7] = {0, 0, 0, 0, 0, 0, 0};  // xx xy xz yy yz zz, denom
-    auto f = [&](const pcr_pt& b) {
+    auto f = [&](const pcr_pt& b, unsigned int) {
         const double dx = b.x - p.x, dy = b.y - p.y, dz = b.z - p.z;
         if ((dx * dx + dy * dy) + dz * dz <= r2_in) {
             const double w = 1.0 / (double)counts[b.id];
@@ -97,14 +96,9 @@ __global__ void __launch_bounds__(256) iss_cov_kernel(pcr_grid_view gv, long lon
             m[6] += w;
         }
     };
-    iss_visit_block(gv, p.x, p.y, p.z, gl, f);
+    ball_visit<BALL_LANES>(gv, p.x, p.y, p.z, gl, f);
 #pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int off = IG / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        m[k] = v;
-    }
+    for (int k = 0; k < 7; ++k) m[k] = ball_lanes_sum(m[k]);
     if (gl == 0) {
         double ev[3];
         const double inv = 1.0 / m[6];  // the point itself is a neighbour: denom > 0
@@ -194,21 +188,13 @@ extern "C" int pcr_iss(pcr_ctx* ctx, const pcr_cloud* cloud, double radius, doub
     hipSetDevice(ctx->device);
     const int64_t n = cloud->n;
     pcr_index_guard idx(ctx);   // (every scratch block and the index go back on every return path)
-    const double cell_req = radius * (1.0 + 1e-9);   // block of 27 cells covers the ball with rounding slack
-    int rc = pcr_index_build(ctx, cloud, PCR_INDEX_GRID, cell_req, &idx.h);
+    int rc = ball_grid(ctx, cloud, radius, "pcr_iss", idx, /*as_stored=*/true);
     if (rc) return rc;
-    // The index keeps 2^18 level-0 cells per axis and coarsens the cell of a cloud whose extent is more than 2^18 radii.  The
-    // 3x3x3 block would still cover the ball, but no longer be of its size: both passes would read every point of 27 cells many
-    // radii wide.  That is refused (it never was: this test asked for a SMALLER cell, which the planner never gives).
-    if (idx->cell > cell_req || idx->cell < radius * (1.0 - 1e-12)) {
-        ctx->last_error = "pcr_iss: the cloud's extent exceeds 2^18 radii; the grid cannot hold a cell of the radius";
-        return PCR_E_UNSUPPORTED;
-    }
     pcr_dev_block b_counts(ctx), b_lam(ctx);
     if ((rc = b_counts.alloc(sizeof(int) * n)) || (rc = b_lam.alloc(sizeof(double) * 3 * n))) return rc;
     int* const d_counts = b_counts.as<int>();
     double* const d_lam = b_lam.as<double>();
-    const unsigned grid = (unsigned)((n * IG + 255) / 256);
+    const unsigned grid = ball_blocks(n);
     const bool want_kp = keypoints_out && n_keypoints_out;
     const bool dev_nms = want_kp && max_keypoints >= 0 && max_keypoints < ISS_NMS_MAX;   // otherwise the host loop over a heap of the candidates
     pcr_dev_block b_cand(ctx), b_rec(ctx), b_tmp(ctx);

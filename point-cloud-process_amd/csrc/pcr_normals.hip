@@ -19,7 +19,7 @@
 #include <string>
 #include <utility>
 #include <vector>
-#include "pcr_grid_dev.h"
+#include "pcr_ball_visit.h"
 #include "pcr_linalg.h"
 
 constexpr int NK_MAX = 16;
@@ -79,12 +79,7 @@ __global__ void __launch_bounds__(256) pca_sum_kernel(const pcr_pt* __restrict__
         }
     }
 #pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        double v = m[k];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-        m[k] = v;
-    }
+    for (int k = 0; k < 6; ++k) m[k] = wave_sum_all(m[k]);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0)
         for (int k = 0; k < 6; ++k) s[wave][k] = m[k];
@@ -105,19 +100,17 @@ normals_kernel(pcr_grid_view gv, long long n, double* __restrict__ normals /* by
     unsigned int bp[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) { bd[k] = DBL_MAX; bi[k] = 0x7fffffffffffffffll; bp[k] = POS_NONE; }
-    bool clamped = false;
-    const int cx = cell_coord(p.x, gv.lo[0], gv.inv_cell0, &clamped);
-    const int cy = cell_coord(p.y, gv.lo[1], gv.inv_cell0, &clamped);
-    const int cz = cell_coord(p.z, gv.lo[2], gv.inv_cell0, &clamped);
+    int cx, cy, cz;
+    const bool clamped = ball_centre_cell(gv, p.x, p.y, p.z, &cx, &cy, &cz);
+    // (the walk of ball_visit<1>, kept written out: through the shared walker the top-K registers are allocated differently and
+    // K = 8, 11 and 16 lose a wave per SIMD -- profiles/ball_walk_resources.md)
     for (int c = 0; c < 27; ++c) {
-        const unsigned int nx = (unsigned int)(cx + c % 3 - 1), ny = (unsigned int)(cy + (c / 3) % 3 - 1), nz = (unsigned int)(cz + c / 9 - 1);
-        if (nx > (unsigned int)PCR_COORD_MAX || ny > (unsigned int)PCR_COORD_MAX || nz > (unsigned int)PCR_COORD_MAX) continue;
         unsigned int s, e;
-        if (!lookup_cell(gv.table[0], gv.mask[0], nx, ny, nz, &s, &e)) continue;
-        for (unsigned int j0 = s; j0 < e; j0 += 4) {   // four records per trip, requested together
+        if (!ball_cell_run(gv, cx, cy, cz, c, &s, &e)) continue;
+        for (unsigned int j0 = s; j0 < e; j0 += 4) {
             pcr_pt rec[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {   // (assigned on every path: conditionally unassigned records become loop-carried registers)
+            for (int u = 0; u < 4; ++u) {
                 rec[u] = pcr_pt{0.0, 0.0, 0.0, 0};
                 if (j0 + u < e) rec[u] = gv.pts[j0 + u];
             }

@@ -121,9 +121,8 @@ __device__ static void ransac_eval(const ransac_args& a, const ransac_state* __r
             const double dis = sqrt((x * x + y * y) + z * z);
             if (dis < a.max_dist) { ++good; e2 += dis * dis; }
         }
-        e2 = wave_sum(e2);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) good += __shfl_xor(good, off, 64);
+        e2 = wave_sum_all(e2);
+        good = wave_sum_all(good);
         if (lane == 0) {
             const int hl = h_base + l;
             inl[hl] = good;

@@ -26,6 +26,25 @@ static inline int pcr_sort_pairs_arena(pcr_ctx* ctx, K* keys_in, K* keys_out, V*
     return PCR_OK;
 }
 
+// the positions 0 .. n - 1 whose flag is set, ascending -> out[0 .. *d_count) (rocprim::select over a counting iterator): the
+// temporary's size asked for, the temporary taken from the arena (`temp` owns it, as above), the select enqueued.  `flags`: any iterator
+// (an array on the device, or a transform iterator that computes the flag); Out: the integer type of the positions.  `who`: the caller's
+// name for the text of a HIP error ("who (select): ...").
+template <typename Flags, typename Out>
+static inline int pcr_select_positions(pcr_ctx* ctx, Flags flags, size_t n, Out* out, unsigned int* d_count, pcr_dev_block& temp, const char* who = nullptr) {
+    const auto positions = rocprim::counting_iterator<Out>(0);
+    size_t temp_bytes = 0;
+    int rc = PCR_OK;
+    hipError_t e = rocprim::select(nullptr, temp_bytes, positions, flags, out, d_count, n, ctx->stream);
+    if (e == hipSuccess && (rc = temp.alloc(temp_bytes)) == PCR_OK) e = rocprim::select(temp.p, temp_bytes, positions, flags, out, d_count, n, ctx->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) {
+        ctx->last_error = (who ? std::string(who) + " (select): " : std::string("rocprim::select: ")) + hipGetErrorString(e);
+        return PCR_E_HIP;
+    }
+    return PCR_OK;
+}
+
 template <typename K>
 struct head_flag {  // position i starts a group of equal keys
     const K* keys;
@@ -33,16 +52,9 @@ struct head_flag {  // position i starts a group of equal keys
 };
 
 // group heads of n sorted keys = positions whose key differs from the previous one -> heads[0 .. *n_groups): one fused flag + scan +
-// scatter (rocprim::select over a counting iterator with a computed flag), instead of a flag kernel, a scan and a scatter
+// scatter (the select with a computed flag), instead of a flag kernel, a scan and a scatter
 template <typename K>
 static inline int pcr_group_heads(pcr_ctx* ctx, const K* sorted_keys, size_t n, unsigned int* heads, unsigned int* n_groups, pcr_dev_block& temp) {
-    const head_flag<K> flag_op{sorted_keys};
-    auto positions = rocprim::counting_iterator<unsigned int>(0u);
-    auto flags = rocprim::make_transform_iterator(positions, flag_op);
-    size_t temp_bytes = 0;
-    int rc;
-    PCR_HIP(ctx, rocprim::select(nullptr, temp_bytes, positions, flags, heads, n_groups, n, ctx->stream));
-    if ((rc = temp.alloc(temp_bytes))) return rc;
-    PCR_HIP(ctx, rocprim::select(temp.p, temp_bytes, positions, flags, heads, n_groups, n, ctx->stream));
-    return PCR_OK;
+    const auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<unsigned int>(0u), head_flag<K>{sorted_keys});
+    return pcr_select_positions(ctx, flags, n, heads, n_groups, temp);
 }

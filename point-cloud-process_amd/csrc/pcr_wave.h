@@ -118,6 +118,21 @@ __device__ static inline double wave_object_sum_f64(double p) {
     return readlane_f64(p, 0);
 }
 
+// Wave sum by the xor butterfly, lane pairs 32 apart, then 16 .. 1: every lane ends with the same bits.  (Not wave_total_f64: that adds
+// in another order and leaves the total in lane 63; the results that go through here are pinned to this order.)  All 64 lanes active.
+__device__ static inline double wave_sum_all(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ static inline int wave_sum_all(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ static inline bool finite3(double x, double y, double z) { return x - x == 0.0 && y - y == 0.0 && z - z == 0.0; }
+
 // LDS hand-off between the lanes of ONE wave: LDS operations of a wave execute in order, so no hardware wait is
 // needed, but the compiler must neither forward a lane's own earlier store to its load nor move accesses across
 __device__ static inline void wave_sync() {

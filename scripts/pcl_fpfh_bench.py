@@ -10,10 +10,10 @@ For context, no target (it follows Open3D's rules: hybrid neighbourhood capped a
 ``compute_fpfh_at_rows`` at the same rows, where the keypoints are rows.  And once, on the same machine's host, the NumPy / cKDTree
 restatement (tests/pcl_fpfh_checks.py) of the 400-row set, with the largest difference between the two.
 
-    python scripts/pcl_fpfh_bench.py [--reps 10] [--no-host] [--out profiles/pcl_fpfh_bench.json] [--merge-read-m OTHER.json]
+    python scripts/pcl_fpfh_bench.py [--reps 10] [--no-host] [--out profiles/pcl_fpfh_bench.json]
 
---merge-read-m: OTHER.json is this script's output from a library built with -DPCR_FPFH_PCL_READ_M (PCR_LIB_PATH=...), the A/B build
-that reads M back and sizes the SPFH block by it; its wall and device medians are stored next to this run's under "sizing".
+("sizing" in the committed profiles/pcl_fpfh_bench.json is the one measurement of a retired A/B build that read M back and sized the SPFH
+block by it: DESIGN.md section 3.6.0.1.  A fresh run of this script does not write it.)
 """
 import argparse
 import ctypes as C
@@ -70,7 +70,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-host", action="store_true", help="skip the NumPy / cKDTree restatement")
-    ap.add_argument("--merge-read-m", metavar="JSON")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pcl_fpfh_bench.json"))
     a = ap.parse_args()
     points = np.ascontiguousarray(pcp.synthetic.kitti_like_scan(N)[:, :3], dtype=np.float64)
@@ -121,12 +120,6 @@ def main():
                                    "max_abs_difference_float32_rows": float(np.abs(f[both] - ref["values"][both].astype(np.float32)).max()),
                                    "clean_share": float((ref["margin"] > 1e-9).mean())}
         print(json.dumps(out["host_restatement"]), flush=True)
-    if a.merge_read_m:
-        with open(a.merge_read_m) as fh:
-            other = json.load(fh)
-        out["sizing"] = {"kept": "the (M,33) block sized by n, no read of M in front of the SPFH launch",
-                         "read_m_build": {k: {"wall_ms": v["wall_ms"], "device_ms": v["device_ms"]} for k, v in other["sets"].items()},
-                         "sized_by_n": {k: {"wall_ms": v["wall_ms"], "device_ms": v["device_ms"]} for k, v in out["sets"].items()}}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(out, fh, indent=1)
