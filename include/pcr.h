@@ -385,6 +385,63 @@ PCR_API int pcr_fpfh_pcl(pcr_ctx* ctx, const pcr_cloud* surface, const double* n
                          const double* keypoints /* (m,3), host */, int64_t m, double radius, double* features_out /* (m,33) binary64 */,
                          int32_t* counts_out /* m, or NULL: |B(x)| */, int64_t* n_spfh_out /* or NULL: M */);
 
+/* SHOT352 at keypoint positions: featureSHOT352(pointcloud, keypoints, compute_normal_k, feature_radius) and
+ * featureSHOT352WithNormal(pointcloud, normals, keypoints, feature_radius) (keypoints.cpp:187-235,282-291) are pcr_normals_knn followed
+ * by pcr_shot352, or pcr_shot352 alone.  The rules below ARE the definition (restated in NumPy by tests/shot_checks.py):
+ * parity with PCL's binary32 output is unpinned.  The conventions of the section hold: binary64 on the stored coordinates, per-row
+ * arrays by caller row, results independent of the lay-out of the records, PCR_E_UNSUPPORTED for a cloud whose extent exceeds 2^18
+ * radii, the ball B(x) of pcr_fpfh_pcl with no cap.  Every dot product is taken in the written order (a0*b0 + a1*b1) + a2*b2 and nothing is
+ * contracted into a fused multiply-add: the hard decisions below are then the same bits wherever they are evaluated.
+ *
+ * Local reference frame at keypoint x (any finite coordinates, on the surface or not; SHOTLocalReferenceFrameEstimation): K = |B(x)|;
+ *   for j in B(x): v_j = p_j - x, d2_j = (v0*v0 + v1*v1) + v2*v2, d_j = sqrt(d2_j), w_j = r - d_j.  M = (sum w_j v_j v_j^T) / (sum w_j):
+ *   six moments ((w_j v_a) v_b each) and the weight sum, each moment divided by the weight sum.  K < 5, or a weight sum that is not
+ *   positive (every row at distance r): the frame is 9 NaN and the descriptor 352 NaN.  Eigenvalues e0 <= e1 <= e2 of M; the x axis
+ *   is the unit eigenvector of e2, the z axis that of e0, each first given the sign that makes its component of largest magnitude
+ *   positive (the first such of equal magnitudes): rows AT the keypoint count as plus for a and for -a, so both can satisfy the rule
+ *   that follows, and the frame must not depend on the eigen solver.  Sign of an axis a: P = #{j in B(x) : v_j.a >= 0} (the zero vector counts as
+ *   plus), s = 2P - K; s < 0: a is negated; s > 0: it stays; s == 0: of the five neighbours of ranks K/2-2 .. K/2+2 (integer division)
+ *   in ascending (d2_j, caller row) order, those with v_j.a > 0 (strictly) are counted, and a is negated when they are fewer than 3.
+ *   x and z are decided independently; y = z cross x, taken after both signs.  The frame is stored as rows x, y, z: (m,9) row-major.
+ *   The moment sums run in a fixed order that is a function of the surface in caller-row order, of the radius and of x's grid cell
+ *   only (pcr_fpfh_pcl's contract): a call is repeatable to the bit and a keypoint does not depend on the others.
+ *
+ * Histogram, 352 = 32 volumes x 11 slots, from a frame (rows X, Y, Z axes) with nine finite entries; any other frame: 352 NaN.
+ *   Constants: r4 = 0.25 r, r2 = 0.5 r, r34 = 0.75 r; q4, q2, q34, q78 = the doubles nearest pi/4, pi/2, 3 pi/4, 7 pi/8.
+ *   A neighbour j in B(x) is SKIPPED when a component of its normal n_j is not finite or when d2_j == 0.  Otherwise
+ *     c = clamp(n_j.Z, -1, 1);  b = ((1.0 + c) * 10) / 2;  X = v_j.Xaxis, Y = v_j.Yaxis, Z = v_j.Zaxis, each set to 0 when its
+ *     magnitude is < 1e-30;  d = sqrt(d2_j).
+ *   Volume: bit4 = (Y > 0) || (Y == 0 && X < 0);  bit3 = ((X > 0) || (X == 0 && Y > 0)) ? !bit4 : bit4;
+ *     desc = ((bit4 << 3) + (bit3 << 2)) << 1;  if (X*Y > 0 || X == 0) desc += (|X| >= |Y|) ? 0 : 4; else desc += (|X| > |Y|) ? 4 : 0;
+ *     desc += (Z > 0) ? 1 : 0;  desc += (d > r2) ? 2 : 0;  sel = desc >> 2 (the azimuth sector, centre -q78 + q4*sel).
+ *   Cosine: step = floor(b + 0.5) (0..10), rho = b - step, vol = 11 desc, W = 1 - |rho|;
+ *     rho > 0: h[vol + (step + 1) % 10] += rho;  else: h[vol + (step - 1 + 10) % 10] += -rho.
+ *   Radial: d > r2: t = (d - r34) / r2;  d > r34: W += 1 - t;  else W += 1 + t and h[11 (desc - 2) + step] += -t.
+ *           else:   t = (d - r4) / r2;   d < r4:  W += 1 + t;  else W += 1 - t and h[11 (desc + 2) + step] += t.
+ *   Elevation: theta = acos(clamp(Z / d, -1, 1)).
+ *           Z <= 0: u = (theta - q34) / q2;  theta > q34: W += 1 - u;  else W += 1 + u and h[11 (desc + 1) + step] += -u.
+ *           else:   u = (theta - q4) / q2;   theta < q4:  W += 1 + u;  else W += 1 - u and h[11 (desc - 1) + step] += u.
+ *   Azimuth, only when X != 0 or Y != 0: a = clamp((atan2(Y, X) - (-q78 + q4 * sel)) / q4, -0.5, 0.5);
+ *           a > 0: W += 1 - a and h[11 ((desc + 4) % 32) + step] += a;  else W += 1 + a and h[11 ((desc - 4 + 32) % 32) + step] += -a.
+ *   Last: h[vol + step] += W.
+ *   Accumulation: every added value v enters as the integer rint(v * 2^32) (ties to even; W once, after its binary64 sum in the order
+ *   above), the integers are summed as 64-bit integers -- exact in any order, no overflow below 2^28 rows in a ball -- and
+ *   h_b = (double)integer * 2^-32.  Output: out_b = h_b / sqrt(sum h_b^2), the sum in bin order to within rounding.  A zero norm (every
+ *   neighbour skipped) gives 352 NaN: PCL's 0/0.  An x that is not finite: count 0, NaN frame, NaN descriptor.
+ *
+ * pcr_shot_lrf: frames_out (m,9); counts_out (m, may be NULL) = |B(x)|.
+ * pcr_shot352: normals (n,3) by caller row and keypoints (m,3), on the host; features_out (m,352) row-major binary64 (PCL's float is
+ *   this rounded once).  frames_in NULL: the frames above are computed.  frames_in (m,9): it replaces the frame stage
+ *   (setInputReferenceFrames) -- whatever K is; a row with an entry that is not finite gives 352 NaN.  frames_out (may be NULL) echoes
+ *   the frames used: features_out with frames_in = an earlier call's frames_out has that call's bytes.  NULL handles or arrays, m < 0,
+ *   m > 2^31 - 1, or a radius that is not a finite positive number: PCR_E_INVALID before anything is launched or allocated.  m == 0:
+ *   PCR_OK, nothing written.  An empty surface: PCR_E_EMPTY.                                                                         */
+PCR_API int pcr_shot_lrf(pcr_ctx* ctx, const pcr_cloud* surface, const double* keypoints /* (m,3), host */, int64_t m, double radius,
+                         double* frames_out /* (m,9) */, int32_t* counts_out /* m, or NULL */);
+PCR_API int pcr_shot352(pcr_ctx* ctx, const pcr_cloud* surface, const double* normals /* (n,3) by caller row, host */,
+                        const double* keypoints /* (m,3), host */, int64_t m, double radius, const double* frames_in /* (m,9), or NULL: computed */,
+                        double* features_out /* (m,352) binary64 */, double* frames_out /* (m,9), or NULL */, int32_t* counts_out /* m, or NULL */);
+
 /* ---------------------------------------------------------- PCA / normals
  * pcr_pca: Pca_and_Voxel_filter/pca_normal.py:10-36 PCA(data, sort=True):
  * eigen-decomposition of np.cov of the cloud (divisor n-1); eigvals_out

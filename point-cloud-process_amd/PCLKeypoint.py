@@ -144,8 +144,7 @@ def _no_descriptor(name):
     if name.startswith("featureFPFH33"):
         raise NotImplementedError(f"{name} is not routed yet: the PCL-rule FPFH descriptor is pcl_features.fpfh33 / fpfh33_with_normal (same arguments), "
                                   "compute_fpfh_feature the Open3D-rule one")
-    raise NotImplementedError(f"{name} needs PCL's own descriptor rules (its SHOT reference frames and binning are unpinned here); the PCL-rule FPFH descriptor "
-                              "is pcl_features.fpfh33")
+    raise NotImplementedError(f"{name} is not routed yet: the PCL-rule SHOT descriptor is pcl_features.shot352 / shot352_with_normal (same arguments)")
 
 
 def featureFPFH33(pointcloud, keypoints, compute_normal_k=10, feature_radius=1.0):

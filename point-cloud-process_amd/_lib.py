@@ -375,6 +375,10 @@ SIGNATURES = {
     "pcr_normals_knn": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _dp]),
     # (ctx, surface, normals, keypoints, m, radius, features, counts | NULL, n_spfh | NULL)
     "pcr_fpfh_pcl": (C.c_int, [_vp, _vp, _dp, _dp, C.c_int64, C.c_double, _dp, _ip, _lp]),
+    # (ctx, surface, keypoints, m, radius, frames, counts | NULL)
+    "pcr_shot_lrf": (C.c_int, [_vp, _vp, _dp, C.c_int64, C.c_double, _dp, _ip]),
+    # (ctx, surface, normals, keypoints, m, radius, frames_in | NULL, features, frames_out | NULL, counts | NULL)
+    "pcr_shot352": (C.c_int, [_vp, _vp, _dp, _dp, C.c_int64, C.c_double, _dp, _dp, _dp, _ip]),
     "pcr_pca": (C.c_int, [_vp, _vp, _dp, _dp, _dp]),
     "pcr_normals": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _ip]),
     "pcr_normals_hybrid": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_int, _dp, _dp]),

@@ -4,6 +4,10 @@ normals they rest on, ``estimate_normals_knn``.  The rules are stated in include
 COORDINATES searched against the cloud as search surface, the neighbourhood is the radius ball alone with no cap, the weighted sum is
 normalised and nothing is added to it.  PCL itself is not used and no version of it is pinned: parity with its binary32 output is
 unpinned.  ``compute_fpfh_feature`` / ``compute_fpfh_at_rows`` follow Open3D's rules and are other descriptors.
+
+The module's second descriptor, SHOT352 (keypoints.cpp:187-235,282-291), takes the same arguments: ``shot352`` (featureSHOT352),
+``shot352_with_normal`` (featureSHOT352WithNormal) and the local reference frames under them, ``shot_lrf``; rules in include/pcr.h
+(pcr_shot_lrf, pcr_shot352), parity with PCL's binary32 output unpinned as well.
 """
 from __future__ import annotations
 
@@ -14,7 +18,7 @@ import numpy as np
 from . import _lib as L
 from .device import DeviceCloud, default_context, points_of
 
-__all__ = ["fpfh33", "fpfh33_with_normal", "estimate_normals_knn"]
+__all__ = ["fpfh33", "fpfh33_with_normal", "estimate_normals_knn", "shot352", "shot352_with_normal", "shot_lrf"]
 
 
 def _cloud(points, ctx):
@@ -102,6 +106,77 @@ def fpfh33(pointcloud, keypoints, compute_normal_k=10, feature_radius=1.0, *, vi
     try:
         nrm, _ = _normals_knn(ctx, cloud, compute_normal_k, viewpoint, False)
         out, info = _fpfh_pcl(ctx, cloud, nrm, kp, feature_radius)
+    finally:
+        if own is not None:
+            own.free()
+    out = out.astype(np.float32)
+    return (out, info) if return_info else out
+
+
+def _shot352(ctx, cloud, nrm, kp, radius, frames=None):
+    """-> ((m,352) float64, info)"""
+    m = kp.shape[0]
+    out = np.empty((m, 352), dtype=np.float64)
+    used = np.empty((m, 9), dtype=np.float64)
+    counts = np.empty(m, dtype=np.int32)
+    L.check(L.lib().pcr_shot352(ctx.handle, cloud.handle, L.dptr(nrm), L.dptr(kp), m, float(radius), L.dptr(frames) if frames is not None else None, L.dptr(out), L.dptr(used),
+                                L.iptr(counts)), ctx.handle, soft=())
+    return out, {"counts": counts, "frames": used.reshape(m, 3, 3), "n": int(cloud.n), "m": int(m)}
+
+
+def shot_lrf(pointcloud, keypoints, radius=1.0, *, ctx=None, return_counts=False):
+    """SHOTLocalReferenceFrameEstimation at the ``keypoints`` -- (m,>=3) coordinates, on the cloud or not -- over ``pointcloud`` as search
+    surface -> (m,3,3) float64, rows x, y, z.  A ball of fewer than 5 rows, or a keypoint that is not finite: 9 NaN.  ``return_counts``
+    adds the (m,) int32 rows in every ball."""
+    ctx = ctx or default_context()
+    kp = _keypoints(keypoints)
+    cloud, own = _cloud(pointcloud, ctx)
+    try:
+        m = kp.shape[0]
+        frames = np.empty((m, 9), dtype=np.float64)
+        counts = np.empty(m, dtype=np.int32)
+        L.check(L.lib().pcr_shot_lrf(ctx.handle, cloud.handle, L.dptr(kp), m, float(radius), L.dptr(frames), L.iptr(counts)), ctx.handle, soft=())
+    finally:
+        if own is not None:
+            own.free()
+    frames = frames.reshape(m, 3, 3)
+    return (frames, counts) if return_counts else frames
+
+
+def shot352_with_normal(pointcloud, normals, keypoints, feature_radius=1.0, *, frames=None, ctx=None, return_info=False):
+    """featureSHOT352WithNormal (keypoints.cpp:214-235) -> float32 (m,352): the SHOT descriptor of the ``keypoints`` -- (m,>=3)
+    coordinates, on the cloud or not -- over ``pointcloud`` as search surface with its per-row ``normals`` (N,3).  A keypoint with fewer
+    than 5 rows within ``feature_radius``, one that is not finite, or one whose neighbours all lack a normal gets 352 NaN.  ``frames``
+    (m,3,3) or (m,9): reference frames to use instead of the computed ones (setInputReferenceFrames).  ``return_info`` adds {"counts":
+    (m,) int32 rows in every ball, "frames": (m,3,3) the frames used, "n": cloud rows, "m": keypoints}."""
+    ctx = ctx or default_context()
+    kp = _keypoints(keypoints)
+    cloud, own = _cloud(pointcloud, ctx)
+    try:
+        nrm = L.as_f64(np.asarray(normals, dtype=np.float64).reshape(-1, 3))
+        if nrm.shape[0] != cloud.n:
+            raise ValueError("normals do not match the cloud")
+        if frames is not None:
+            frames = L.as_f64(np.asarray(frames, dtype=np.float64).reshape(-1, 9))
+            if frames.shape[0] != kp.shape[0]:
+                raise ValueError("frames do not match the keypoints")
+        out, info = _shot352(ctx, cloud, nrm, kp, feature_radius, frames)
+    finally:
+        if own is not None:
+            own.free()
+    out = out.astype(np.float32)
+    return (out, info) if return_info else out
+
+
+def shot352(pointcloud, keypoints, compute_normal_k=10, feature_radius=1.0, *, viewpoint=(0.0, 0.0, 0.0), ctx=None, return_info=False):
+    """featureSHOT352 (keypoints.cpp:187-211) -> float32 (m,352): ``estimate_normals_knn(pointcloud, compute_normal_k, viewpoint)``, then
+    ``shot352_with_normal`` with those normals; the cloud is uploaded once."""
+    ctx = ctx or default_context()
+    kp = _keypoints(keypoints)
+    cloud, own = _cloud(pointcloud, ctx)
+    try:
+        nrm, _ = _normals_knn(ctx, cloud, compute_normal_k, viewpoint, False)
+        out, info = _shot352(ctx, cloud, nrm, kp, feature_radius)
     finally:
         if own is not None:
             own.free()
