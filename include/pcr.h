@@ -1241,6 +1241,17 @@ PCR_API int pcr_debug_arena(pcr_ctx* ctx, int64_t out[2]);
 /* diagnostics: the nth next device-scratch allocation on this context is refused (PCR_E_NOMEM), once; nth = 0 disarms.  Only a counter
  * on the host is tested: nothing is launched and no device call is made to fail.  Not for the batch entry points.             */
 PCR_API int pcr_debug_fail_alloc(pcr_ctx* ctx, int nth);
+/* diagnostics: n independent problems through one of the small dense solves that end the hot paths (csrc/pcr_linalg.h), one problem
+ * per device lane, so that tests reach the DEVICE build of each function with inputs no pipeline produces.  ctx == NULL: the same loop
+ * through the host build.  Doubles per problem, row-major matrices:
+ *   op 0  svd3                      in H[9]                          out U[9], s[3], V[9]
+ *   op 1  svd3, warm start          in H[9], V0[9]                   out U[9], s[3], V[9]
+ *   op 2  sym3_jacobi               in upper triangle 00 01 02 11 12 22   out A after [9], Q[9]
+ *   op 3  kabsch_from_moments       in m[18], origin[3]              out R[9], t[3], cost
+ *   op 4  the same with V_io        in m[18], origin[3], V[9]        out R[9], t[3], cost, V[9]
+ *   op 5  point2plane_solve         in A_upper[21], b[6]             out x[6], U[16], ok (1.0 / 0.0)
+ * n == 0: PCR_OK, nothing written.  PCR_E_INVALID: n < 0, n > 65536, an unknown op, in or out NULL.                                */
+PCR_API int pcr_debug_linalg(pcr_ctx* ctx, int op, const double* in, int64_t n, double* out);
 PCR_API int pcr_profile_enable(pcr_ctx* ctx, int on);
 /* diagnostics of the LAST correspondence search on this context (Registration/main.py:116-121 is the step they describe):
  * out[0] = queries the brute-force MFMA sweep could not prove and re-did with the exact direct-form sweep;

@@ -455,6 +455,8 @@ SIGNATURES = {
     "pcr_debug_read": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int64]),
     "pcr_debug_arena": (C.c_int, [_vp, _lp]),
     "pcr_debug_fail_alloc": (C.c_int, [_vp, C.c_int]),
+    # (ctx or NULL for the host build, op, n x in doubles, n, n x out doubles): include/pcr.h lists the doubles per op
+    "pcr_debug_linalg": (C.c_int, [_vp, C.c_int, _dp, C.c_int64, _dp]),
     "pcr_profile_enable": (C.c_int, [_vp, C.c_int]),
     "pcr_profile_read": (C.c_int, [_vp, _dp, C.POINTER(C.c_int)]),
     "pcr_search_stats": (C.c_int, [_vp, _lp]),

@@ -3,7 +3,10 @@
 // pcr_icp_step.h opt back in (#pragma clang fp contract(fast)): on the device the step is ONE lane's chain of ~1 000 dependent
 // binary64 operations at the end of every ICP pass, a quarter of them multiply-add pairs -- fused they shorten the pass by 0.7 us
 // of 37 (same-box A/B).  Every device kernel compiles the same expressions the same way (the fused batch stays bitwise equal
-// to the per-pair path: tested), and nothing here is compared bitwise with the host build of the same functions (goldens: 1e-9).
+// to the per-pair path: tested), and nothing here is compared bitwise with the host build of the same functions (goldens: 1e-9;
+// both builds are held to a 60-digit reference at their edges through pcr_debug_linalg: tests/linalg_checks.py).
+// Valid scale: svd3_rotate forms alpha * beta and d^2, fourth powers of the entries, so the entries of H must keep their fourth power
+// in binary64's range, roughly 1e-75 to 1e75 (read from the code, not measured; tested to 1e+-60).
 #pragma once
 #include <cmath>
 #include <cstring>
