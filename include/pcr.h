@@ -341,6 +341,54 @@ PCR_API int pcr_iss_pcl(pcr_ctx* ctx, const pcr_cloud* cloud, double salient_rad
                         double gamma32, int min_neighbors, double* e3_out /* n */, int32_t* counts_out /* n */,
                         int32_t* keypoints_out, int64_t capacity, int64_t* n_keypoints_out);
 
+/* SIFT-3D, the scale-aware detector of the module: keypointSift (keypoints.cpp:85-109, keypoints.hpp:167-178), pcl::SIFTKeypoint
+ * (detectKeypoints, computeScaleSpace, findScaleSpaceExtrema) on the field the wrapper selects, the y coordinate.  As above the rules
+ * below ARE the definition, restated in NumPy by tests/sift_checks.py; parity with PCL's binary32 output is unpinned.  The section's
+ * conventions hold: binary64 on the stored coordinates, per-row arrays by caller row, results independent of the lay-out of the records,
+ * sums in a fixed order that is a function of the cloud in caller-row order and of the radius only (a call is repeatable to the bit),
+ * d2 = (dx*dx + dy*dy) + dz*dz, no operation contracted into an FMA.
+ *
+ * Scales of an octave, base scale b, q = n_scales_per_octave: S = q + 3 scales sigma_s = b * pow(2.0, (s - 1.0) / q), s = 0 .. S-1,
+ *   computed on the host, and from them sigma2_s = sigma_s * sigma_s, lim_s = 9.0 * sigma2_s, h_s = -0.5 / sigma2_s, each rounded as
+ *   written.  1 <= q <= 13 (S <= 16); any other q: PCR_E_UNSUPPORTED with a message.  pcr_sift_scales returns the sigma_s (host only).
+ *
+ * Response and DoG, v_j = coordinate `field` (0, 1, 2: x, y, z; the wrapper's is 1) of row j: the ball of row i is every row j with
+ *   d2 <= lim_{S-1}, walked through a grid of cell 3 sigma_{S-1} (extent above 2^18 cells: PCR_E_UNSUPPORTED).  For each scale s, over the
+ *   rows of the ball with d2 <= lim_s:  w = exp(d2 * h_s), num_s += v_j * w, den_s += w;  resp_s = num_s / den_s.  Row i is in every sum
+ *   (w = 1), so den_s >= 1.  D[i][c] = resp_{c+1} - resp_c, c = 0 .. C-1, C = q + 2.  counts[i] = rows in the ball.
+ *
+ * Extrema: N(i) = the min(25, n) rows smallest in (d2, caller row), row i among them.  For c = 1 .. C-2 and val = D[i][c], the entry
+ *   (i, c) is a keypoint iff fabs(val) >= min_contrast and it is
+ *     a minimum: val < D[i][c-1] && val < D[i][c+1], and for no j in N(i) and no e in {c-1, c, c+1} is val > D[j][e], or
+ *     a maximum: the mirrored statement.
+ *   A tie with a neighbour keeps the entry, a tie with the row's own adjacent column does not.  Entries are in ascending (row, c); the
+ *   keypoint's scale is sigma_c.
+ *
+ * Octave loop (min_scale, n_octaves, q, min_contrast): scale = min_scale, cloud = the input; for each octave cloud =
+ *   voxel_down_sample(cloud, scale), stop if it holds fewer than 25 rows, run the octave above at b = scale, scale *= 2.  Keypoints are in
+ *   ascending (octave, row, c) and their positions are the octave's down-sampled rows.
+ *   STATED DEPARTURE: the down-sampling is mode 2 of pcr_voxel_filter_cloud (lattice origin min - leaf/2, running sum in input order, rows
+ *   by voxel key).  PCL's VoxelGrid anchors its lattice at multiples of the leaf and orders its rows otherwise.
+ *
+ * Rows with a coordinate that is not finite: the result for such a row is unspecified (the walk stays in bounds); the Python layer
+ * refuses them.  PCR_E_INVALID, before anything is launched or allocated: NULL handles, n_octaves < 1, a min_scale / base_scale that is
+ * not finite and positive, a min_contrast that is NaN or negative, a field outside 0..2.  An empty cloud: PCR_E_EMPTY.
+ *
+ * pcr_sift_octave: one octave on the cloud as given (no down-sampling).  pcr_sift_extrema: the extrema stage alone on a caller's table
+ * (n x C, host, 3 <= C <= 15).  pcr_sift: the loop; the octaves' clouds stay on the device.  keypoints_out: x, y, z, scale per keypoint;
+ * octave_out / row_out (or NULL): its octave and its row of that octave's cloud; octave_sizes_out (n_octaves, or NULL): the rows of each
+ * octave's cloud, 0 for the octaves not run.  The capacity rule is pcr_harris3d's: on more entries than `capacity`, *n_out is the needed
+ * number, nothing is written to the per-keypoint arrays and the call returns PCR_E_UNSUPPORTED (the per-row outputs are complete).        */
+PCR_API int pcr_sift_scales(double base_scale, int n_scales_per_octave, double* scales_out /* n_scales_per_octave + 3 */);
+PCR_API int pcr_sift_octave(pcr_ctx* ctx, const pcr_cloud* cloud, double base_scale, int n_scales_per_octave, double min_contrast, int field,
+                            double* dog_out /* n*C, or NULL */, int32_t* counts_out /* n, or NULL */, int32_t* rows_out, int32_t* cols_out,
+                            int64_t capacity, int64_t* n_out);
+PCR_API int pcr_sift_extrema(pcr_ctx* ctx, const pcr_cloud* cloud, const double* dog /* n*C by row, host */, int n_columns, double min_contrast,
+                             int32_t* rows_out, int32_t* cols_out, int64_t capacity, int64_t* n_out);
+PCR_API int pcr_sift(pcr_ctx* ctx, const pcr_cloud* cloud, double min_scale, int n_octaves, int n_scales_per_octave, double min_contrast, int field,
+                     double* keypoints_out /* capacity*4 */, int32_t* octave_out, int32_t* row_out, int64_t capacity, int64_t* n_out,
+                     int64_t* octave_sizes_out);
+
 /* PCL-rule descriptors of the same module: featureFPFH33(pointcloud, keypoints, compute_normal_k, feature_radius) and
  * featureFPFH33WithNormal(pointcloud, normals, keypoints, feature_radius) (keypoints.cpp:112-184,272-281) are pcr_normals_knn followed
  * by pcr_fpfh_pcl, or pcr_fpfh_pcl alone.  As for the keypoints, the rules below ARE the definition (restated in NumPy by

@@ -57,6 +57,8 @@ from . import PCLKeypoint  # noqa: F401
 from .PCLKeypoint import keypointHarris3D, keypointIss  # noqa: F401
 from . import pcl_features  # noqa: F401
 from .pcl_features import estimate_normals_knn, fpfh33, fpfh33_with_normal, shot352, shot352_with_normal, shot_lrf  # noqa: F401
+from . import pcl_keypoints  # noqa: F401
+from .pcl_keypoints import sift_extrema, sift_keypoints, sift_octave, sift_scales  # noqa: F401
 from .dbscan import DBSCAN  # noqa: F401
 from .clustering import clustering, ground_segmentation, segment_and_cluster  # noqa: F401
 from . import objects  # noqa: F401

@@ -371,6 +371,13 @@ SIGNATURES = {
     "pcr_harris3d": (C.c_int, [_vp, _vp, _dp, C.POINTER(HarrisParams), _dp, _ip, _ip, C.c_int64, _lp, _dp, _dp, _ip]),
     # (ctx, cloud, salient radius, non-max radius, gamma21, gamma32, min_neighbors, scores, counts, keypoints, capacity, n_keypoints)
     "pcr_iss_pcl": (C.c_int, [_vp, _vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _ip, _ip, C.c_int64, _lp]),
+    "pcr_sift_scales": (C.c_int, [C.c_double, C.c_int, _dp]),
+    # (ctx, cloud, base scale, scales per octave, min contrast, field, dog | NULL, counts | NULL, rows, columns, capacity, n)
+    "pcr_sift_octave": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, _ip, C.c_int64, _lp]),
+    # (ctx, cloud, dog, columns, min contrast, rows, columns, capacity, n)
+    "pcr_sift_extrema": (C.c_int, [_vp, _vp, _dp, C.c_int, C.c_double, _ip, _ip, C.c_int64, _lp]),
+    # (ctx, cloud, min scale, octaves, scales per octave, min contrast, field, keypoints, octave | NULL, row | NULL, capacity, n, octave sizes | NULL)
+    "pcr_sift": (C.c_int, [_vp, _vp, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _ip, _ip, C.c_int64, _lp, _lp]),
     # (ctx, cloud, k, viewpoint | NULL, normals, curvature | NULL)
     "pcr_normals_knn": (C.c_int, [_vp, _vp, C.c_int, _dp, _dp, _dp]),
     # (ctx, surface, normals, keypoints, m, radius, features, counts | NULL, n_spfh | NULL)

@@ -4,6 +4,7 @@
 //   pcr_iss.hip        both ISS passes                                        lane-group walk (grid over the cloud as stored)
 //   pcr_harris.hip     position covariance, normal covariance, suppression    lane-group walk;  refine: wave walk
 //   pcr_fpfh_pcl.hip   mark, SPFH, FPFH                                       wave walk, the last two with the ballot compaction
+//   pcr_sift.hip       DoG pass, the 25 nearest rows of a candidate           wave walk
 //   pcr_normals.hip    normals_kernel<K>                                      the cell lookup (its own cell size and its own loop, see there)
 // (gather_hybrid of pcr_features.hip keeps its own cell lookup and ballot compaction beside its flat list: the note there says why.)
 // Lane-group walk: BALL_LANES lanes per point, lane gl owns the cells gl, gl + LANES, ...; it meets them in that order and a cell's records

@@ -373,6 +373,10 @@ PCR_HIDDEN int pcr_wait_flag(pcr_ctx* ctx, double* flag_us);
 // pcr_knn between its upload and its download (pcr_knn.hip): q queries (3 doubles each) resident at d_q, results left at d_idx / d_dist
 // [i * k, ...); enqueued on the context's stream, any q and k
 PCR_HIDDEN int pcr_knn_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t q, int k, int* d_idx, double* d_dist);
+// the exact descent alone (knn_kernel, any k) for the queries d_list[0 .. *d_list_count) of the q resident ones: the list and its length
+// stay on the device (at most q entries), results at d_idx / d_dist [i * k, ...) of the listed queries only; enqueued, no wait
+PCR_HIDDEN int pcr_knn_list_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t q, int k, int* d_idx, double* d_dist, const int* d_list,
+                                const unsigned int* d_list_count);
 PCR_HIDDEN int pcr_d2h_small_enqueue(pcr_ctx* ctx, void* mapped_host_dst, const void* dev_src, size_t bytes);
 // whole ICP loop on the device (grid index); fills res like the host loop of pcr_icp
 PCR_HIDDEN int pcr_grid_icp_loop(pcr_ctx* ctx, const pcr_index* idx, pcr_cloud* qc, const pcr_icp_params* params, const double T0[16],

@@ -703,6 +703,14 @@ int pcr_knn_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t
     return PCR_OK;
 }
 
+// The descent for the listed queries only.  (A grid over all q: the list's length is only known on the device.)
+int pcr_knn_list_dev(pcr_ctx* ctx, const pcr_index* index, const double* d_q, int64_t q, int k, int* d_idx, double* d_dist, const int* d_list,
+                     const unsigned int* d_list_count) {
+    hipLaunchKernelGGL(knn_kernel, dim3((unsigned)((q + 3) / 4)), dim3(256), 0, ctx->stream, index->view, d_q, (long long)q, k, d_idx, d_dist, d_list, d_list_count);
+    PCR_HIP(ctx, hipGetLastError());
+    return PCR_OK;
+}
+
 extern "C" {
 
 int pcr_radius_small(pcr_ctx* ctx, const pcr_index* index, const double* queries, int q, double radius, int64_t cap, int64_t* counts_out,
